@@ -47,6 +47,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICRO
 KERNELS = ["e264_dbkparam2_kernel", "e264_pred_kernel", "e264_intra_kernel", "e264_deblock_kernel"]
 SIDE_QUEUE_DEFAULT = 0
 DBK_BYTES = 144  # deblocking parameters per macroblock (edge264_amd/csrc/e264_kernels.h)
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: both arrays together, headers included
+DUMP_SEED = 2024  # --dump-outputs: the sample positions of stream k come from default_rng((DUMP_SEED, k))
 
 
 def parse_args(argv=None):
@@ -78,7 +80,12 @@ def parse_args(argv=None):
                     "groups whose submissions overlap on the GPU")
     ap.add_argument("--capture", default=None, help="capture file (edge264_amd/replay.py): its first stream's packets replace the synthetic GOP, "
                     "so that the kernels are timed on real motion / partition statistics (tools/make_capture.py writes one from a .264)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the pictures the last timed step left in "
+                    "rank 0's streams to DIR/pictures.npy and DIR/positions.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(n: int) -> int:
@@ -559,6 +566,29 @@ def system_leg(cpu, seconds=12.0):
     return res
 
 
+def dump_outputs(out_dir, streams, parsed, frame_nb):
+    """--dump-outputs: what a caller of the timed path receives from its last step, i.e. the decoded pictures still held in each
+    stream's DPB (the last picture written into each slot the GOP writes, oldest first), as samples 0..255.
+      pictures.npy   float32 [stream, picture, sample]
+      positions.npy  float64 [stream, sample]: byte offsets of the samples into the picture (Y plane, then the chroma planes)
+    When every sample of every picture does not fit into DUMP_BYTES, stream k keeps the same K positions in all its pictures,
+    drawn without replacement by default_rng((DUMP_SEED, k)): the same arguments give the same positions in every run."""
+    last = {int(q.hdr["dst_slot"]): f for f, q in enumerate(parsed)}
+    slots = sorted(last, key=last.get)
+    n, m = len(streams), len(slots)
+    k = min(frame_nb, (DUMP_BYTES - 1024) // (n * (4 * m + 8)))  # 1024: the two .npy headers
+    pictures = np.empty((n, m, k), np.float32)
+    positions = np.empty((n, k), np.float64)
+    for i, st in enumerate(streams):
+        idx = np.arange(frame_nb) if k == frame_nb else np.sort(np.random.default_rng((DUMP_SEED, i)).choice(frame_nb, k, replace=False))
+        positions[i] = idx
+        for j, s in enumerate(slots):
+            pictures[i, j] = st.download(s)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pictures.npy"), pictures)
+    np.save(os.path.join(out_dir, "positions.npy"), positions)
+
+
 def main() -> int:
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -725,6 +755,8 @@ def main() -> int:
     ev_ms = dev.event_elapsed_ms(0, 1)
     frames_per_step = total_frames // args.steps
     value = total_frames / elapsed
+    if rank == 0 and args.dump_outputs:  # before the verification below refills the slots
+        dump_outputs(args.dump_outputs, streams, parsed, frame_nb)
 
     # ---- bit-exactness at full size (untimed): EVERY stream, EVERY frame of one more GOP against the CPU oracle ----
     verify, bit_exact = None, None

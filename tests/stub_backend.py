@@ -1,7 +1,10 @@
 """TEST INFRASTRUCTURE: a device that does nothing, with edge264_amd.backend's Python surface, so that bench.py's rank
 launcher, stream sharding and max-over-ranks reduction can run as N gloo ranks on a machine without GPUs
-(E264_BENCH_BACKEND=tests.stub_backend).  It never produces samples: bench.py skips verification and baselines for it."""
+(E264_BENCH_BACKEND=tests.stub_backend).  It never decodes (download() hands back what fill() wrote): bench.py skips
+verification and baselines for it."""
 import time
+
+import numpy as np
 
 IS_STUB = True
 RUN_RECON, RUN_DEBLOCK, RUN_ALL = 1, 2, 3
@@ -63,7 +66,7 @@ class Device:
 
 class Stream:
     def __init__(self, dev, w, h):
-        pass
+        self.fills = {}
 
     def close(self):
         pass
@@ -75,4 +78,7 @@ class Stream:
         pass
 
     def fill(self, slot, value):
-        pass
+        self.fills[slot] = value
+
+    def download(self, slot):
+        return np.full(self.frame_bytes, self.fills[slot], np.uint8)

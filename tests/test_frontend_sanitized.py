@@ -12,7 +12,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/edge264.c") or shutil.which("gcc") is None, reason="builds the front end from /root/reference")
+@pytest.mark.skipif(not os.path.exists("/root/reference/src/edge264.c") or shutil.which("gcc") is None, reason="runs only where the reference tree exists: it builds the front end from the reference's sources "
+                    "with sanitizers, which the repository may not carry")
 def test_no_sanitizer_report_in_the_emitters(tmp_path):
     out = tmp_path / "report.txt"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sanitize", "run.py"), "--flips", "2", "--out", str(out)],

@@ -244,3 +244,41 @@ def test_bench_distributed_path_on_one_gpu():
     if os.path.isdir("/sys/devices/system/node/node0") and numa["numa_node"] < 0:
         # the platform has NUMA nodes in sysfs: the GPU's node must have been found through its PCI address
         pytest.fail(f"NUMA node of the GPU not found: {numa}")
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_decoded_pictures(tmp_path):
+    """bench.py --dump-outputs writes what the timed steps decoded: every dumped picture equals the oracle's decoding of the same seeded
+    synthetic GOP (bench.py's skw; no picture of the GOP refers to one of the step before, so the last step decodes as the first)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle.pyoracle import Oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    w, h, gop, n_streams, n_var = 20, 6, "IPPP", 3, 2
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--streams", str(n_streams), "--gop", gop,
+                        "--width-mbs", str(w), "--height-mbs", str(h), "--variants", str(n_var), "--no-cpu-baseline", "--no-other-configs",
+                        "--no-host-packets", "--no-system", "--no-staggered", "--no-single-stream", "--no-same-input",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(p.stdout.strip().splitlines()[-1])["bit_exact"] is True
+    pics, pos = np.load(tmp_path / "pictures.npy"), np.load(tmp_path / "positions.npy")
+    skw = dict(t8x8=True, i_kinds=(P.MB_I4x4, P.MB_I8x8, P.MB_I16x16), num_refs=2, residual_prob=0.3)
+    for v in range(n_var):
+        pk = synth.StreamSynth(w, h, seed=1234 + v, **skw).gop(gop)
+        hdrs = [P.Packet(q).hdr for q in pk]
+        nb = int(hdrs[0]["plane_size_Y"]) + int(hdrs[0]["plane_size_C"])
+        last = {int(hd["dst_slot"]): f for f, hd in enumerate(hdrs)}
+        slots = sorted(last, key=last.get)
+        dpb = [np.full(nb + 64, 128, np.uint8) for _ in range(max(slots) + 1)] + [None] * (31 - max(slots))
+        orc = Oracle()
+        for q in pk:
+            orc.decode_frame(q, dpb, 3)
+        assert pics.shape == (n_streams, len(slots), nb)
+        for k in range(v, n_streams, n_var):
+            idx = pos[k].astype(np.int64)
+            for j, s in enumerate(slots):
+                assert np.array_equal(pics[k, j], dpb[s][:nb][idx]), (k, s)

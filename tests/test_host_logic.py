@@ -317,6 +317,35 @@ def test_bench_says_when_the_synthetic_content_is_overridden():
             assert "2 distinct GOPs" in d["config"]["workload"]
 
 
+def test_bench_dump_outputs_is_sampled_within_budget_and_repeatable(tmp_path):
+    """--dump-outputs DIR (stub device, whose pictures are the fill value): 1080p pictures of 8 streams do not fit into 64 MB, so every
+    picture is sampled; the arrays are float32 / float64, stay within the budget, and a second run with the same arguments writes the
+    same arrays.  The line reports the --steps it was given and ms_per_step."""
+    import json
+    import numpy as np
+    env = dict(os.environ, E264_BENCH_BACKEND="tests.stub_backend", OMP_NUM_THREADS="1", PYTHONPATH=ROOT)
+    env.pop("WORLD_SIZE", None)
+    got = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--streams", "8", "--gop", "IPP", "--variants", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["pictures.npy", "positions.npy"]
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 * 10**6
+        pics, pos = (np.load(tmp_path / run / f) for f in files)
+        assert pics.dtype == np.float32 and pos.dtype == np.float64
+        frame_nb = 1920 * 1088 * 3 // 2
+        assert pics.shape[:2] == (8, 3) and pos.shape == (8, pics.shape[2]) and 0 < pics.shape[2] < frame_nb
+        assert (np.diff(pos, axis=1) > 0).all() and pos.min() >= 0 and pos.max() < frame_nb
+        assert (pics == 128).all()
+        got.append((pics, pos))
+    assert all(np.array_equal(x, y) for x, y in zip(*got))
+
+
 def test_bench_line_prices_the_kernels_against_valu_issue():
     """at the configuration the canned SQ counters were taken on (256 streams, IPPPPPPP, 120 x 68) the line carries, per kernel,
     the VALU wave-instructions per launch, their share of the chip's issue slots at the live kernel time and lane instructions per sample; `bound`
@@ -342,11 +371,21 @@ def test_bench_line_prices_the_kernels_against_valu_issue():
 
 
 def test_numa_helpers():
-    from edge264_amd.sharding import bind_rank_to_gpu_socket, parse_cpulist
+    from edge264_amd.sharding import bind_rank_to_gpu_socket, gpu_numa_cpus, parse_cpulist
     assert parse_cpulist("0-3,8,10-11\n") == [0, 1, 2, 3, 8, 10, 11] and parse_cpulist("") == []
     before = os.sched_getaffinity(0)
-    info = bind_rank_to_gpu_socket(0)   # no GPU here: node unknown, affinity untouched
-    assert info["bound"] is False and os.sched_getaffinity(0) == before
+    node, cpus = gpu_numa_cpus(0)
+    want = before & set(cpus)
+    try:
+        info = bind_rank_to_gpu_socket(0)
+        if node < 0 or not want or want == before:
+            # no GPU here (node unknown), or the launcher's CPUs are already the GPU's node: affinity untouched
+            assert info["bound"] is False and os.sched_getaffinity(0) == before
+        else:
+            # a GPU whose NUMA node is known: the rank narrows itself to that node's CPUs among those it was granted
+            assert info == {"numa_node": node, "bound": True, "cpus": len(want)} and os.sched_getaffinity(0) == want
+    finally:
+        os.sched_setaffinity(0, before)  # the rest of the session keeps the CPUs it was started with
 
 
 def test_product_library_reports_no_build_switches_and_ablation_builds_are_refused(monkeypatch):
