@@ -75,6 +75,7 @@ def load_library():
         "e264hip_set_option": (i, [vp, C.c_char_p, i]),
         "e264hip_build_flags": (C.c_char_p, []),
         "e264hip_frame_device_ptr": (vp, [vp, i]),
+        "e264hip_launch_counts": (i, [vp, C.POINTER(C.c_uint64), i, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -99,7 +100,14 @@ EXPORTED_SYMBOLS = [
     "e264hip_packet_buffer", "e264hip_frame_wait", "e264hip_frame_download", "e264hip_packet_upload",
     "e264hip_packet_free", "e264hip_packet_check", "e264hip_packet_compact_bound", "e264hip_packet_compact", "e264hip_packet_expand", "e264hip_submit_batch", "e264hip_submit_batch_host", "e264hip_submit_batch_pinned", "e264hip_host_alloc", "e264hip_host_free", "e264hip_batch_create", "e264hip_batch_submit", "e264hip_batch_free", "e264hip_event_record", "e264hip_event_elapsed_ms", "e264hip_event_query",
     "e264hip_kernel_timing", "e264hip_kernel_time_ms", "e264hip_set_option", "e264hip_build_flags", "e264hip_frame_device_ptr",
+    "e264hip_launch_counts",
 ]
+
+# slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
+# other slot the pictures that went through one kernel form
+LAUNCH_COUNT_NAMES = ("n_cus expand dbkp_small dbkp_general dbkp_side1 dbkp_side2 pred "
+                      "intra4_bitmap intra8_bitmap intra16_bitmap intra4_nobitmap intra8_nobitmap intra16_nobitmap "
+                      "intra_split intra_planes_split intra_planes_alone dbk_planes dbk2_6 dbk2_7 dbk2_8 dbk2_10 dbk2_12 dbk_2 dbk_4 dbk_7 dbk_8").split()
 
 
 def _check(L, r: int, what: str) -> None:
@@ -166,6 +174,14 @@ class Device:
 
     def set_option(self, name: str, value: int) -> int:
         return self.L.e264hip_set_option(self.h, name.encode(), value)
+
+    def launch_counts(self, reset: bool = False) -> dict:
+        """Pictures per kernel form since the device was opened or last reset (LAUNCH_COUNT_NAMES), and the CU count as "n_cus"."""
+        out = (C.c_uint64 * len(LAUNCH_COUNT_NAMES))()
+        r = self.L.e264hip_launch_counts(self.h, out, len(out), int(reset))
+        if r != len(LAUNCH_COUNT_NAMES):
+            raise BackendError(f"e264hip_launch_counts: {r} slots, this binding knows {len(LAUNCH_COUNT_NAMES)}")
+        return {k: int(v) for k, v in zip(LAUNCH_COUNT_NAMES, out)}
 
     def upload_packet(self, pkt: bytes) -> "DevicePacket":
         return DevicePacket(self, pkt)

@@ -138,7 +138,7 @@ struct E264Device {
 	hipStream_t qc = nullptr;  // download queue
 	int waves;                 // waves per frame workgroup of the deblocking kernel (5 macroblock rows each): 2, 4, 7 or 8
 	int intra_waves;           // waves per frame workgroup of the intra kernel (1 macroblock row each)
-	std::atomic<int> max_lane{0}; // highest lane a stream was ever bound to
+	std::atomic<int> lane_streams[NQ] = {}; // live streams bound to each lane (open, bind_lane, close): the lanes in use are those with one
 	int n_cus;                 // compute units of the device
 	int split_planes;          // option "split_planes" (default 1): the split-off pictures' intra pass with luma and chroma on two workgroups (e264_intra_planes_kernel)
 	int split_intra;           // option "split_intra" (default 1): in a submission that mixes I pictures with others, their intra pass runs on q2 from the start (E264Fork.n_nopred)
@@ -147,7 +147,8 @@ struct E264Device {
 	hipStream_t q2[NQ];        // one second queue per compute lane (+ its fork / join events): lanes must not share one (their split submissions would queue behind each other)
 	hipEvent_t forked[NQ], joined[NQ];
 	hipEvent_t lane_ev[NQ];    // e264hip_event_record: joins the other lanes into lane 0
-	std::mutex lock;           // kernel launches + their timing marks + the submission event ring
+	std::mutex lock;           // kernel launches + their timing marks + the submission event ring + launch_counts
+	uint64_t launch_counts[E264_LC_COUNT] = {}; // pictures per kernel form (e264hip_launch_counts; slot E264_LC_N_CUS unused here)
 	std::mutex batch_lock;     // host batches: job ring, staging
 	hipEvent_t ev[16];
 	// per-launch kernel timing
@@ -505,6 +506,7 @@ API int e264hip_stream_open(E264Device *dev, E264Stream **out)
 		return fail(ENOMEM, "slot table");
 	}
 	hipMemsetAsync(s->d_table, 0, sizeof(uint8_t *) * E264_MAX_SLOTS, lane_of(s));
+	dev->lane_streams[0].fetch_add(1, std::memory_order_relaxed);
 	*out = s;
 	return 0;
 }
@@ -516,9 +518,9 @@ API int e264hip_stream_bind_lane(E264Stream *s, int lane)
 	if (set_device(s->dev)) return EIO;
 	// what the old lane still has queued for this stream (table updates, fills, submissions) must be over before the new one starts
 	HIPCHK(hipStreamSynchronize(lane_of(s)), EIO);
+	s->dev->lane_streams[lane].fetch_add(1, std::memory_order_relaxed);
+	s->dev->lane_streams[s->lane].fetch_sub(1, std::memory_order_relaxed);
 	s->lane = lane;
-	int seen = s->dev->max_lane.load(std::memory_order_relaxed);
-	while (seen < lane && !s->dev->max_lane.compare_exchange_weak(seen, lane, std::memory_order_relaxed)) {}
 	return 0;
 }
 
@@ -558,6 +560,7 @@ API void e264hip_stream_close(E264Stream *s)
 		if (s->tab_ev[i]) hipEventDestroy(s->tab_ev[i]);
 	mem_release(dev, s->tab_pin, sizeof(uint8_t *) * E264_MAX_SLOTS * E264Stream::NTAB, true, 0, 0);
 	mem_release(dev, s->d_table, sizeof(uint8_t *) * E264_MAX_SLOTS, false, 0, 0);
+	dev->lane_streams[s->lane].fetch_sub(1, std::memory_order_relaxed);
 	delete s;
 }
 
@@ -860,6 +863,14 @@ static int ensure_expand(E264Stream *s, size_t area)
 	return s->d_expand ? 0 : fail(ENOMEM, "hipMalloc expansion buffer");
 }
 
+// The highest lane that has a live stream (0 if none): what the rules below mean by "the lanes in use"
+static int highest_lane_in_use(E264Device *dev)
+{
+	for (int i = E264Device::NQ - 1; i > 0; i--)
+		if (dev->lane_streams[i].load(std::memory_order_relaxed) > 0) return i;
+	return 0;
+}
+
 // Launches the kernels over a job table that already lives in HBM, on compute lane `lane`.
 // n_nopred: the table's LAST n_nopred jobs hold no inter / PCM macroblock (0: unknown or none)
 static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int max_mbs, int max_tiles, int mode, uint64_t *serial_out = nullptr, int n_nopred = 0)
@@ -868,7 +879,8 @@ static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int m
 	hipEvent_t *marks = nullptr;
 	// (not with more than two lanes in use: lanes and second queues then share the runtime's hardware queues -- four by default, GPU_MAX_HW_QUEUES -- and a lane's
 	// kernels wait behind another lane's 2.7-ms intra pass: 38.7 k against 52.0 k frames/s without the split, tools/stagger_probe.py, profiles/r06_ablations.txt item 16)
-	const bool split = (dev->split_intra == 2 || (dev->split_intra && dev->max_lane.load(std::memory_order_relaxed) < 2)) && dev->q2[lane] && n_nopred > 0 && n_nopred < n;
+	const int max_lane = highest_lane_in_use(dev);
+	const bool split = (dev->split_intra == 2 || (dev->split_intra && max_lane < 2)) && dev->q2[lane] && n_nopred > 0 && n_nopred < n;
 	// Two workgroups per picture (luma, chroma: e264_intra_planes_kernel) for the pictures whose intra pass stands alone -- while they are few: each takes a whole CU
 	// (125 KB of LDS) from the prediction kernel of the others, and with more than ~320 other pictures in the submission their kernels outlast a one-workgroup pass
 	// anyway (tools/stagger_probe.py: 256 pictures out of phase 72.4 -> 84.9 k frames/s; 512: 88.7 -> 86.9 k without this rule; profiles/r06_ablations.txt item 18)
@@ -878,7 +890,7 @@ static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int m
 	// ... a kernel that has the lane to itself (an all-intra batch's intra pass, every batch's deblocking) may take every CU: 64 streams 38.2 -> 42.8 k frames/s,
 	// 128 streams 61.6 -> 69.8 k (gpurun_out/pa1; E264_PLANES_ALONE overrides for A/B)
 	static const int alone_env = getenv("E264_PLANES_ALONE") ? atoi(getenv("E264_PLANES_ALONE")) : 0;
-	const int cu_alone = alone_env > 0 ? alone_env : dev->n_cus / (dev->max_lane.load(std::memory_order_relaxed) + 1); // (the lanes in use run beside each other: a lane's share)
+	const int cu_alone = alone_env > 0 ? alone_env : dev->n_cus / (max_lane + 1); // (the lanes in use run beside each other: a lane's share)
 	if (dev->split_planes && (mode & E264_RUN_NO_PRED) && 2 * n <= cu_alone) planes |= 2;
 	if (dev->split_planes && 2 * n <= cu_alone) planes |= 4; // ... and the deblocking kernel's luma and chroma groups (one stream: a P picture 0.89 ms, of which that kernel is most)
 	E264Fork fork = {dev->side_queue || split || planes ? dev->q2[lane] : nullptr, dev->forked[lane], dev->joined[lane], nullptr, dev->side_queue, split ? n_nopred : 0, planes};
@@ -893,7 +905,9 @@ static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int m
 		m.side = !split && dev->side_queue && fork.aux != nullptr && (mode & 2); // (the parameter kernel's own marks; in a split submission it stays on the lane and the intra phase [2..3] holds the join)
 		marks = m.e; fork.amarks = m.a;
 	}
-	HIPCHK(e264_launch_frames(d_jobs, n, max_mbs, max_tiles, mode, dev->waves | dev->intra_waves << 8, dev->q[lane], marks, &fork), EIO);
+	uint64_t counts[E264_LC_COUNT] = {};
+	HIPCHK(e264_launch_frames(d_jobs, n, max_mbs, max_tiles, mode, dev->waves | dev->intra_waves << 8, dev->q[lane], marks, &fork, counts), EIO);
+	for (int i = 0; i < E264_LC_COUNT; i++) dev->launch_counts[i] += counts[i];
 	const uint64_t serial = ++dev->serial;
 	const int idx = (int)(serial % E264Device::NEV);
 	if (dev->sub_ev[idx] && hipEventRecord(dev->sub_ev[idx], dev->q[lane]) == hipSuccess) { dev->sub_serial[idx] = serial; dev->sub_lane[idx] = lane; }
@@ -1315,7 +1329,10 @@ static int submit_host_impl(E264Device *dev, E264Stream *const *streams, const v
 	else
 		e = hipMemcpyAsync(jr.pd, jr.ph, total, hipMemcpyHostToDevice, up);
 	if (e == hipSuccess) e = hipMemcpyAsync(jr.d, jr.h, sizeof(E264Job) * n, hipMemcpyHostToDevice, up);
-	if (e == hipSuccess && any_wire) e = e264_launch_expand(jr.d, n, max_mbs, up);
+	if (e == hipSuccess && any_wire) {
+		e = e264_launch_expand(jr.d, n, max_mbs, up);
+		if (e == hipSuccess) { std::lock_guard<std::mutex> g(dev->lock); dev->launch_counts[E264_LC_EXPAND] += (uint64_t)n; }
+	}
 	if (e == hipSuccess && up != q) {
 		e = hipEventRecord(jr.up, up);
 		if (e == hipSuccess) e = hipStreamWaitEvent(q, jr.up, 0);
@@ -1341,6 +1358,15 @@ static int submit_host_impl(E264Device *dev, E264Stream *const *streams, const v
 
 // Timing events are recorded on lane 0 AFTER everything queued on the other lanes so far (lane 0 waits for them): with one
 // lane in use that is the plain event on the queue of the kernels, with several it brackets all of them.
+API int e264hip_launch_counts(E264Device *dev, uint64_t *out, int n, int reset)
+{
+	if (!dev || (n > 0 && !out)) { fail(EINVAL, "launch_counts arguments"); return -1; }
+	std::lock_guard<std::mutex> g(dev->lock);
+	for (int i = 0; i < n && i < E264_LC_COUNT; i++) out[i] = i == E264_LC_N_CUS ? (uint64_t)dev->n_cus : dev->launch_counts[i];
+	if (reset) memset(dev->launch_counts, 0, sizeof(dev->launch_counts));
+	return E264_LC_COUNT;
+}
+
 API int e264hip_event_record(E264Device *dev, int idx)
 {
 	if (!dev || idx < 0 || idx >= 16) return fail(EINVAL, "event index");

@@ -3,6 +3,7 @@
 #define E264_KERNELS_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/edge264_hip.h" // (E264_LC_*: the slots of e264_launch_frames' counts)
 
 // One job = one coded frame of one stream: its command packet (already in HBM) and the
 // table of the stream's DPB slots (device pointers, E264_MAX_SLOTS entries, NULL if unallocated).
@@ -36,8 +37,9 @@ struct E264Fork { hipStream_t aux; hipEvent_t forked, joined; hipEvent_t *amarks
 extern "C" int e264_pred_tiles(int width_mbs, int height_mbs);
 // build-time switches of the kernels ("" = product build; e264hip_build_flags hands it out)
 extern "C" const char *e264_kernel_build_flags(void);
+// counts: NULL, or E264_LC_COUNT slots (include/edge264_hip.h) to which the pictures of every form launched here are added
 extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int max_mbs, int max_tiles, int mode, int waves, hipStream_t stream, hipEvent_t *marks,
-	const E264Fork *fork);
+	const E264Fork *fork, uint64_t *counts);
 
 // e264_expand_kernel alone (a batch's wire packets, on the queue of its upload); E264_RUN_EXPAND in e264_launch_frames' mode runs it in front of the four instead
 extern "C" hipError_t e264_launch_expand(const E264Job *jobs, int n_jobs, int max_mbs, hipStream_t stream);

@@ -503,24 +503,32 @@ extern "C" hipError_t e264_launch_expand(const E264Job *jobs, int n_jobs, int ma
 }
 
 extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int max_mbs, int max_tiles, int mode, int waves, hipStream_t stream, hipEvent_t *marks,
-	const E264Fork *fork)
+	const E264Fork *fork, uint64_t *counts)
 {
 	if (n_jobs <= 0)
 		return hipSuccess;
+	auto count = [&](int slot, int n) { if (counts) counts[slot] += (uint64_t)n; };
 	// wire packets first (before the marks: they bracket the four kernels; the whole-run clocks contain this one)
-	if (mode & E264_RUN_EXPAND)
-		e264_launch_expand(jobs, n_jobs, max_mbs, stream);
+	if (mode & E264_RUN_EXPAND) {
+		const hipError_t e = e264_launch_expand(jobs, n_jobs, max_mbs, stream);
+		if (e != hipSuccess)
+			return e;
+		count(E264_LC_EXPAND, n_jobs);
+	}
 	// marks (optional): 5 events recorded before / between / after the four launches
 	if (marks) hipEventRecord(marks[0], stream);
 	const bool dbkp = (mode & 2) != 0;
 	const bool no_l1 = (mode & E264_RUN_NO_L1) != 0; // no packet of the batch predicts from list 1: the parameter kernel's small form (eight workgroups per CU)
 	const int intra_waves_ = waves >> 8 ? waves >> 8 : waves & 255;
-	auto launch_intra = [&](const E264Job *j, int n, hipStream_t q, int use_bitmap) {
+	// split_slot: where the split-off pictures are counted (any wave count) instead of under the kernel's own slot
+	auto launch_intra = [&](const E264Job *j, int n, hipStream_t q, int use_bitmap, int split_slot = -1) {
+		const int slot = use_bitmap ? E264_LC_INTRA4_BITMAP : E264_LC_INTRA4_NOBITMAP; // (then + 1: 8 waves, + 2: 16 waves)
 		switch (intra_waves_) {
 		case 4: hipLaunchKernelGGL(e264_intra_kernel<4>, dim3(n), dim3(256), 0, q, j, use_bitmap); break;
 		case 16: hipLaunchKernelGGL(e264_intra_kernel<16>, dim3(n), dim3(1024), 0, q, j, use_bitmap); break;
 		default: hipLaunchKernelGGL(e264_intra_kernel<8>, dim3(n), dim3(512), 0, q, j, use_bitmap); break;
 		}
+		count(split_slot >= 0 ? split_slot : slot + (intra_waves_ == 4 ? 0 : intra_waves_ == 16 ? 2 : 1), n);
 	};
 	// a submission that mixes pictures without prediction work (the table's last n_nopred jobs: I pictures) with others: their intra pass starts NOW on the
 	// second queue (E264Fork.n_nopred, e264_kernels.h); the rest of this function then sees the other jobs only, up to deblocking
@@ -530,8 +538,12 @@ extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int ma
 		hipEventRecord(fork->forked, stream);
 		hipStreamWaitEvent(fork->aux, fork->forked, 0);
 		if (marks) hipEventRecord(fork->amarks[0], fork->aux);
-		if ((fork->planes & 1) && intra_waves_ == 16) hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n_split, 2), dim3(1024), 0, fork->aux, jobs + n_front);
-		else launch_intra(jobs + n_front, n_split, fork->aux, 0);
+		if ((fork->planes & 1) && intra_waves_ == 16) {
+			hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n_split, 2), dim3(1024), 0, fork->aux, jobs + n_front);
+			count(E264_LC_INTRA_PLANES_SPLIT, n_split);
+		} else {
+			launch_intra(jobs + n_front, n_split, fork->aux, 0, E264_LC_INTRA_SPLIT);
+		}
 		if (marks) hipEventRecord(fork->amarks[1], fork->aux);
 		hipEventRecord(fork->joined, fork->aux);
 	}
@@ -545,6 +557,8 @@ extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int ma
 		if (marks) hipEventRecord(fork->amarks[0], fork->aux);
 		if (no_l1) hipLaunchKernelGGL(e264_dbkparam2_kernel<false>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, fork->aux, jobs);
 		else hipLaunchKernelGGL(e264_dbkparam2_kernel<true>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, fork->aux, jobs);
+		count(no_l1 ? E264_LC_DBKP_SMALL : E264_LC_DBKP_GENERAL, n_jobs);
+		count(where == 2 ? E264_LC_DBKP_SIDE2 : E264_LC_DBKP_SIDE1, n_jobs);
 		if (marks) hipEventRecord(fork->amarks[1], fork->aux);
 		hipEventRecord(fork->joined, fork->aux);
 	};
@@ -553,41 +567,48 @@ extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int ma
 	else if (dbkp && !side) {
 		if (no_l1) hipLaunchKernelGGL(e264_dbkparam2_kernel<false>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, stream, jobs);
 		else hipLaunchKernelGGL(e264_dbkparam2_kernel<true>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, stream, jobs);
+		count(no_l1 ? E264_LC_DBKP_SMALL : E264_LC_DBKP_GENERAL, n_jobs);
 	}
 	if (marks) hipEventRecord(marks[1], stream);
 	// an all-intra batch (every picture of an I launch: E264_RUN_NO_PRED) has nothing for the prediction kernel: 34 816 workgroups that load their records and
 	// leave cost 0.12 ms per launch of 256 pictures; the intra kernel then scans without the bitmap those workgroups would have written
 	const bool no_pred = (mode & E264_RUN_NO_PRED) != 0;
-	if ((mode & 1) && !no_pred)
+	if ((mode & 1) && !no_pred) {
 		hipLaunchKernelGGL(e264_pred_kernel, dim3(max_tiles, n_front), dim3(PT_NT), 0, stream, jobs, mode);
+		count(E264_LC_PRED, n_front);
+	}
 	if (marks) hipEventRecord(marks[2], stream);
 	if (where == 2)
 		launch_side();
 	waves &= 255;
 	if ((mode & 1) && no_pred && fork && (fork->planes & 2) && intra_waves_ == 16) // a FEW pictures, all without prediction work (one stream's I picture): two CUs each
+	{
 		hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n_jobs, 2), dim3(1024), 0, stream, jobs);
-	else if (mode & 1)
+		count(E264_LC_INTRA_PLANES_ALONE, n_jobs);
+	} else if (mode & 1)
 		launch_intra(jobs, n_front, stream, no_pred ? 0 : 1);
 	if (n_split) hipStreamWaitEvent(stream, fork->joined, 0);
 	if (side) hipStreamWaitEvent(stream, fork->joined, 0); // (before the mark: with the parameter kernel beside it, "intra" is the phase both share)
 	if (marks) hipEventRecord(marks[3], stream);
 	if ((mode & 2) && waves == 108 && fork && (fork->planes & 4)) // few pictures: two workgroups each (luma groups, chroma groups)
+	{
 		hipLaunchKernelGGL(e264_deblock2_planes_kernel<8>, dim3(n_jobs, 2), dim3(512), 0, stream, jobs);
-	else if (mode & 2) {
+		count(E264_LC_DBK_PLANES, n_jobs);
+	} else if (mode & 2) {
 		switch (waves) { // waves per picture (default 8, set by the back end); 100 + n: luma / chroma waves (e264_deblock2_kernel)
 #if E264_DBK_GS == 2 // strips of four macroblocks: 12.6 KB of LDS per wave, twelve waves (three per SIMD) fit the CU
-		case 112: hipLaunchKernelGGL(e264_deblock2_kernel<12>, dim3(n_jobs), dim3(768), 0, stream, jobs); break;
-		case 110: hipLaunchKernelGGL(e264_deblock2_kernel<10>, dim3(n_jobs), dim3(640), 0, stream, jobs); break;
+		case 112: hipLaunchKernelGGL(e264_deblock2_kernel<12>, dim3(n_jobs), dim3(768), 0, stream, jobs); count(E264_LC_DBK2_12, n_jobs); break;
+		case 110: hipLaunchKernelGGL(e264_deblock2_kernel<10>, dim3(n_jobs), dim3(640), 0, stream, jobs); count(E264_LC_DBK2_10, n_jobs); break;
 #else
 		case 112: case 110:
 #endif
-		case 108: hipLaunchKernelGGL(e264_deblock2_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); break;
-		case 107: hipLaunchKernelGGL(e264_deblock2_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); break;
-		case 106: hipLaunchKernelGGL(e264_deblock2_kernel<6>, dim3(n_jobs), dim3(384), 0, stream, jobs); break;
-		case 2: hipLaunchKernelGGL(e264_deblock_kernel<2>, dim3(n_jobs), dim3(128), 0, stream, jobs); break;
-		case 4: hipLaunchKernelGGL(e264_deblock_kernel<4>, dim3(n_jobs), dim3(256), 0, stream, jobs); break;
-		case 8: hipLaunchKernelGGL(e264_deblock_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); break;
-		default: hipLaunchKernelGGL(e264_deblock_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); break;
+		case 108: hipLaunchKernelGGL(e264_deblock2_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); count(E264_LC_DBK2_8, n_jobs); break;
+		case 107: hipLaunchKernelGGL(e264_deblock2_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); count(E264_LC_DBK2_7, n_jobs); break;
+		case 106: hipLaunchKernelGGL(e264_deblock2_kernel<6>, dim3(n_jobs), dim3(384), 0, stream, jobs); count(E264_LC_DBK2_6, n_jobs); break;
+		case 2: hipLaunchKernelGGL(e264_deblock_kernel<2>, dim3(n_jobs), dim3(128), 0, stream, jobs); count(E264_LC_DBK_2, n_jobs); break;
+		case 4: hipLaunchKernelGGL(e264_deblock_kernel<4>, dim3(n_jobs), dim3(256), 0, stream, jobs); count(E264_LC_DBK_4, n_jobs); break;
+		case 8: hipLaunchKernelGGL(e264_deblock_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); count(E264_LC_DBK_8, n_jobs); break;
+		default: hipLaunchKernelGGL(e264_deblock_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); count(E264_LC_DBK_7, n_jobs); break;
 		}
 	}
 	if (marks) hipEventRecord(marks[4], stream);

@@ -160,6 +160,21 @@ int  e264hip_kernel_time_ms(E264Device *dev, double *ms4, int *launches);
  * option of the product. */
 int  e264hip_set_option(E264Device *dev, const char *name, int value);
 
+/* Which kernel forms the launcher chose: pictures (jobs, not launches) that went through each form since the device was
+ * opened or last reset, one uint64_t per slot in the order below.  Slot 0 holds the device's compute-unit count instead
+ * (the size rules of the two-workgroup forms depend on it).  The intra slots are exclusive: a picture's intra pass is
+ * counted once, under the split-off forms when it ran on the second queue.  dbkp_side1 / dbkp_side2 count the pictures
+ * whose parameter kernel ran on the second queue (beside prediction / beside intra) on top of dbkp_small / dbkp_general.
+ * Copies min(n, E264_LC_COUNT) slots; reset != 0 zeroes the counters after the copy.  Returns E264_LC_COUNT, or -1. */
+#define E264_LC_NAMES "n_cus expand dbkp_small dbkp_general dbkp_side1 dbkp_side2 pred " \
+	"intra4_bitmap intra8_bitmap intra16_bitmap intra4_nobitmap intra8_nobitmap intra16_nobitmap " \
+	"intra_split intra_planes_split intra_planes_alone dbk_planes dbk2_6 dbk2_7 dbk2_8 dbk2_10 dbk2_12 dbk_2 dbk_4 dbk_7 dbk_8"
+enum { E264_LC_N_CUS, E264_LC_EXPAND, E264_LC_DBKP_SMALL, E264_LC_DBKP_GENERAL, E264_LC_DBKP_SIDE1, E264_LC_DBKP_SIDE2, E264_LC_PRED,
+	E264_LC_INTRA4_BITMAP, E264_LC_INTRA8_BITMAP, E264_LC_INTRA16_BITMAP, E264_LC_INTRA4_NOBITMAP, E264_LC_INTRA8_NOBITMAP, E264_LC_INTRA16_NOBITMAP,
+	E264_LC_INTRA_SPLIT, E264_LC_INTRA_PLANES_SPLIT, E264_LC_INTRA_PLANES_ALONE, E264_LC_DBK_PLANES, E264_LC_DBK2_6, E264_LC_DBK2_7, E264_LC_DBK2_8,
+	E264_LC_DBK2_10, E264_LC_DBK2_12, E264_LC_DBK_2, E264_LC_DBK_4, E264_LC_DBK_7, E264_LC_DBK_8, E264_LC_COUNT };
+int  e264hip_launch_counts(E264Device *dev, uint64_t *out, int n, int reset);
+
 #ifdef __cplusplus
 }
 #endif

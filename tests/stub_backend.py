@@ -32,6 +32,10 @@ class Device:
     def set_option(self, name, value):
         return 0
 
+    def launch_counts(self, reset=False):
+        from edge264_amd.backend import LAUNCH_COUNT_NAMES
+        return {k: 256 if k == "n_cus" else 0 for k in LAUNCH_COUNT_NAMES}
+
     def upload_packet(self, pkt):
         return _Packet(len(pkt))
 

@@ -31,6 +31,24 @@ def test_library_exports_every_header_symbol():
     assert set(names) == set(backend.EXPORTED_SYMBOLS)
 
 
+def test_launch_count_slots_match_header():
+    """e264hip_launch_counts: the slot names of the binding are E264_LC_NAMES of the header, in the order of its E264_LC_* enum,
+    and the stub back end answers with the same keys"""
+    from edge264_amd import backend
+    from tests import stub_backend
+    src = open(os.path.join(ROOT, "include", "edge264_hip.h")).read()
+    m = re.search(r'#define E264_LC_NAMES ((?:"[^"]*"\s*\\?\s*)+)', src)
+    assert m, "E264_LC_NAMES missing from include/edge264_hip.h"
+    names = "".join(re.findall(r'"([^"]*)"', m.group(1))).split()
+    assert tuple(names) == tuple(backend.LAUNCH_COUNT_NAMES)
+    enum = re.search(r"enum \{ (E264_LC_N_CUS.*?) \};", src, re.S).group(1)
+    slots = [e.strip() for e in enum.split(",") if e.strip()]
+    assert slots[-1] == "E264_LC_COUNT"
+    assert [s[len("E264_LC_"):].lower() for s in slots[:-1]] == names
+    stub = stub_backend.Device(0).launch_counts()
+    assert set(stub) == set(names) and stub["n_cus"] > 0
+
+
 def test_no_cpu_fallback_without_gpu():
     """Without a GPU the product path must fail loudly, not fall back to the oracle."""
     import torch
