@@ -10,6 +10,12 @@ per 4x4 block, references pointing at already decoded DPB slots.
 
 Used by tests (small frames, bit-exact HIP vs oracle vs reference kernels)
 and by bench.py (1080p).  Seeded, so every rank / run sees the same bytes.
+
+The range-end options (weight_denoms, weight_range, offset_range, weight_pins,
+scaling_range, level_ends, mv_ends, chroma_qp_offsets) reach the values a
+packet may carry but the default draws never do.  Left unset they draw nothing
+from the generator, so the default bytes stay what bench.py and the seeded
+tests were written against (tests/test_synth_defaults.py).
 """
 from __future__ import annotations
 
@@ -90,6 +96,29 @@ def modes_chroma(a: bool, b: bool, d: bool) -> list[int]:
     return out
 
 
+def range_end_options(r: np.random.Generator) -> dict:
+    """Range-end options (StreamSynth's weight_denoms ... chroma_qp_offsets) drawn from r, each present half the time: what the randomised
+    checking tools (tools/oracle_sweep.py, tools/emu_sweep.py) add to their other draws."""
+    kw = {}
+    if r.random() < 0.5:
+        kw["weight_denoms"] = [(int(r.integers(0, 8)), int(r.integers(0, 8))) for _ in range(int(r.integers(1, 4)))]
+        if r.random() < 0.5:
+            kw["weight_denoms"].append((7, 7))
+    if r.random() < 0.5:
+        kw.update(weight_range=(-128, 127), offset_range=(-128, 127))
+    if r.random() < 0.5:
+        kw["weight_pins"] = float(r.choice([0.1, 0.3, 0.6]))
+    if r.random() < 0.5:
+        kw["scaling_range"] = ((1, 256), (150, 256), (200, 256))[int(r.integers(0, 3))]
+    if r.random() < 0.5:
+        kw["level_ends"] = True
+    if r.random() < 0.5:
+        kw["mv_ends"] = float(r.choice([0.02, 0.1, 0.3]))
+    if r.random() < 0.5:
+        kw["chroma_qp_offsets"] = (int(r.choice([-12, -6, 0, 6, 12])), int(r.choice([-12, -6, 0, 6, 12])))
+    return kw
+
+
 class StreamSynth:
     """Generates the packets of one synthetic stream, frame by frame.
 
@@ -102,7 +131,19 @@ class StreamSynth:
                  slices_per_frame: int = 1, intra_in_inter: float = 0.05, p_skip: float = 0.1,
                  residual_prob: float = 0.3, num_refs: int = 2, mv_range: int = 64, pcm_prob: float = 0.0,
                  stress: bool = False, qp_base: int = 28, i_kinds=(P.MB_I4x4, P.MB_I16x16),
-                 filter_offsets=(0, 0), deblock_idc: int = 0, n_slots: int = 6):
+                 filter_offsets=(0, 0), deblock_idc: int = 0, n_slots: int = 6,
+                 weight_denoms=None, weight_range=(-32, 96), offset_range=(-20, 20), weight_pins: float = 0.0,
+                 scaling_range=(8, 40), level_ends: bool = False, mv_ends: float = 0.0, chroma_qp_offsets=None):
+        """The range-end options:
+        weight_denoms      (luma, chroma) log2 weight denominator pairs, one drawn per explicitly weighted slice (default: each of 3..6)
+        weight_range       explicit weights drawn from [lo, hi]; offset_range: explicit offsets from [lo, hi]
+        weight_pins        probability that an explicit weight is pinned to -128, 127 or the default 1 << denom (the offset then 0, what
+                           a cleared weight flag gives) and an explicit offset to -128 or 127
+        scaling_range      scaling-list entries drawn from [lo, hi)
+        level_ends         per macroblock, one of: the usual levels; int16 ends (+-32767, -32768, +-16000, 127, -128, 128, -129) in
+                           every block including the DC ones; byte-form ends (every AC level in -128..127, -128 and 127 both present)
+        mv_ends            probability that a vector component is pinned near an int16 end (+-32768 quarter samples)
+        chroma_qp_offsets  (Cb, Cr) chroma QP offsets instead of two drawn from -3..3"""
         self.w, self.h = width_mbs, height_mbs
         self.rng = np.random.default_rng(seed)
         self.t8x8, self.scaling, self.weighted, self.deblock = t8x8, scaling, weighted, deblock
@@ -115,7 +156,14 @@ class StreamSynth:
         self.frame_no = 0
         self.refs: list[int] = []  # DPB slots of decoded reference (non-B) frames, newest first
         self.cabac_like = cabac_like
-        self.cqp_off = (int(self.rng.integers(-3, 4)), int(self.rng.integers(-3, 4)))
+        self.weight_denoms = None if weight_denoms is None else [tuple(int(x) for x in p) for p in weight_denoms]
+        self.weight_range, self.offset_range, self.weight_pins = tuple(weight_range), tuple(offset_range), weight_pins
+        self.scaling_range, self.level_ends, self.mv_ends = tuple(scaling_range), level_ends, mv_ends
+        self.lev_mode = 0  # level_ends: 0 usual, 1 int16 ends, 2 byte-form ends (drawn per macroblock)
+        if chroma_qp_offsets is not None:
+            self.cqp_off = (int(chroma_qp_offsets[0]), int(chroma_qp_offsets[1]))
+        else:
+            self.cqp_off = (int(self.rng.integers(-3, 4)), int(self.rng.integers(-3, 4)))
 
     # ---- helpers ---------------------------------------------------------
     def _free_slot(self) -> int:
@@ -131,6 +179,8 @@ class StreamSynth:
         rng = self.rng
         c = np.zeros(n, np.int16)
         N = 4 if n == 16 else 8
+        if self.lev_mode:
+            return self._end_levels(n, N, maxnz, lowfreq)
         if self.stress:
             lim = 2000
         else:
@@ -142,31 +192,59 @@ class StreamSynth:
             c[(x % N) * N + (y % N)] = v if v else 1
         return c
 
+    _INT16_ENDS = (32767, -32768, -32767, 16000, -16000, 127, -128, 128, -129)
+
+    def _end_levels(self, n: int, N: int, maxnz: int, lowfreq: int) -> np.ndarray:
+        """level_ends: int16 ends (lev_mode 1) or byte-form levels with -128 and 127 at the two first AC positions (lev_mode 2)"""
+        rng = self.rng
+        c = np.zeros(n, np.int16)
+        for _ in range(int(rng.integers(1, maxnz + 1))):
+            x, y = int(rng.integers(0, lowfreq)), int(rng.integers(0, lowfreq))
+            if self.lev_mode == 1:
+                v = self._INT16_ENDS[int(rng.integers(0, len(self._INT16_ENDS)))]
+            else:
+                v = int(rng.choice([-128, 127, -127, 126, int(rng.integers(-128, 128))]))
+            c[(x % N) * N + (y % N)] = v if v else 1
+        if self.lev_mode == 2:
+            c[1], c[N] = -128, 127
+        return c
+
     def _slice_params(self, b: P.PacketBuilder, ftype: str, first_mb: int, l0: list[int], l1: list[int]):
         rng = self.rng
         kw = dict(slice_type={"I": 2, "P": 0, "B": 1}[ftype], first_mb=first_mb, cabac=int(self.cabac_like),
                   FilterOffsetA=self.filter_offsets[0], FilterOffsetB=self.filter_offsets[1],
                   disable_deblocking_filter_idc=(self.deblock_idc if self.deblock else 1))
         if self.scaling:
-            kw["weightScale4x4"] = rng.integers(8, 40, (6, 16)).astype(np.uint8)
-            kw["weightScale8x8"] = rng.integers(8, 40, (6, 64)).astype(np.uint8)
+            kw["weightScale4x4"] = rng.integers(*self.scaling_range, (6, 16)).astype(np.uint8)
+            kw["weightScale8x8"] = rng.integers(*self.scaling_range, (6, 64)).astype(np.uint8)
         ew = np.zeros((3, 64), np.int16)
         eo = np.zeros((3, 64), np.int8)
         lwd = cwd = 0
         idc = 0
         if ftype != "I" and self.weighted == 1:
             idc = 1
-            lwd, cwd = int(rng.integers(3, 7)), int(rng.integers(3, 7))
+            if self.weight_denoms is None:
+                lwd, cwd = int(rng.integers(3, 7)), int(rng.integers(3, 7))
+            else:
+                lwd, cwd = self.weight_denoms[int(rng.integers(0, len(self.weight_denoms)))]
             for pl, wd in ((0, lwd), (1, cwd), (2, cwd)):
                 ew[pl, :] = 1 << wd
+            (wlo, whi), (olo, ohi) = self.weight_range, self.offset_range
             for lx, lst in ((0, l0), (1, l1)):
                 for i in range(len(lst)):
                     if rng.random() < 0.7:  # luma_weight_flag
-                        ew[0, lx * 32 + i] = rng.integers(-32, 97)
-                        eo[0, lx * 32 + i] = rng.integers(-20, 21)
+                        ew[0, lx * 32 + i] = rng.integers(wlo, whi + 1)
+                        eo[0, lx * 32 + i] = rng.integers(olo, ohi + 1)
                     if rng.random() < 0.7:  # chroma_weight_flag
-                        ew[1:, lx * 32 + i] = rng.integers(-32, 97, 2)
-                        eo[1:, lx * 32 + i] = rng.integers(-20, 21, 2)
+                        ew[1:, lx * 32 + i] = rng.integers(wlo, whi + 1, 2)
+                        eo[1:, lx * 32 + i] = rng.integers(olo, ohi + 1, 2)
+                    if self.weight_pins:
+                        for pl, wd in ((0, lwd), (1, cwd), (2, cwd)):
+                            if rng.random() < self.weight_pins:
+                                ew[pl, lx * 32 + i] = (-128, 127, 1 << wd)[int(rng.integers(0, 3))]
+                                eo[pl, lx * 32 + i] = 0 if ew[pl, lx * 32 + i] == 1 << wd else eo[pl, lx * 32 + i]
+                            if rng.random() < self.weight_pins and ew[pl, lx * 32 + i] != 1 << wd:
+                                eo[pl, lx * 32 + i] = (-128, 127)[int(rng.integers(0, 2))]
         elif ftype == "B" and self.weighted == 2:
             idc = 2
         iw = np.full((32, 32), 32 + 64, np.uint8)
@@ -222,6 +300,8 @@ class StreamSynth:
                     flags |= P.MBF_EDGE_TOP
             qp = int(np.clip(qp + rng.integers(-2, 3), 10 if not self.stress else 0, 45 if not self.stress else 51))
             qps = (qp, chroma_qp(qp, self.cqp_off[0]), chroma_qp(qp, self.cqp_off[1]))
+            if self.level_ends:
+                self.lev_mode = int(rng.integers(0, 3))
             inter = ftype != "I" and rng.random() >= self.intra_in_inter
             if not inter and rng.random() < self.pcm_prob:
                 b.set_mb(addr, kind=P.MB_PCM, slice_idx=sidx, qp=(0, chroma_qp(0, self.cqp_off[0]), chroma_qp(0, self.cqp_off[1])),
@@ -289,6 +369,11 @@ class StreamSynth:
                         if rng.random() < 0.5:
                             luma_blocks[k] = self._levels(16, qp, 6, 3)
                             nz |= 1 << k
+                if self.lev_mode == 2 and not luma_blocks:  # byte-form ends need an AC block
+                    c = self._levels(16, qp, 4, 3)
+                    c[0] = 0 if kind == P.MB_I16x16 else c[0]
+                    luma_blocks[0] = c if not t8 else np.resize(c, 64)
+                    nz |= 1 if not t8 else 0xf
                 if rng.random() < 0.6:
                     chroma_dc = self._levels(16, qps[1], 4, 4)[:8].copy()
                     chroma_dc[0] |= 1
@@ -324,7 +409,12 @@ class StreamSynth:
         rangemv = self.mv_range * (16 if big else 1)
 
         def mv():
-            return rng.integers(-rangemv, rangemv + 1, 2)
+            v = rng.integers(-rangemv, rangemv + 1, 2)
+            if self.mv_ends:
+                for j in range(2):
+                    if rng.random() < self.mv_ends:
+                        v[j] = (-32768, 32767, -32767 + int(rng.integers(0, 2800)), 32767 - int(rng.integers(0, 2800)))[int(rng.integers(0, 4))]
+            return v
         if ftype == "P":
             use = [(True, False)] * 4
         else:

@@ -97,7 +97,7 @@ class Synth:
     def __init__(self, g, name, W, H, frames, seed, *, t8x8=False, num_refs=2, weighted_pred=0, weighted_bipred=0,
                  slices=1, deblock=(0,), direct_spatial=1, scaling=False, pcm=0.03, qp=28, cqp=(0, 0), level=3.0,
                  intra_in_inter=0.12, skip=0.15, coef_density=0.35, big_levels=0.03, cbp_zero=0.0, cabac=False, tables=None, mvc=False,
-                 crop=None, longterm=False, mmco_at=(), reorder=0.0, aso=False, pps_switch=False, gap_at=()):
+                 crop=None, longterm=False, mmco_at=(), reorder=0.0, aso=False, pps_switch=False, gap_at=(), wp_ends=False):
         self.g, self.name, self.W, self.H = g, name, W, H
         self.frames, self.rng = frames, random.Random(seed)
         self.t8x8, self.num_refs, self.wp, self.wbp = t8x8, num_refs, weighted_pred, weighted_bipred
@@ -115,6 +115,7 @@ class Synth:
         self.reorder = reorder      # probability that a P/B slice moves another short-term picture to the head of list 0
         self.aso = aso              # arbitrary slice order: the slices of a picture are written in shuffled order
         self.pps_switch = pps_switch  # two picture parameter sets (own chroma QP offsets + scaling matrix), alternating per picture
+        self.wp_ends = wp_ends      # pred_weight_table at the ends of its ranges: denominators 7 (default weight 128), weights / offsets -128 / 127
 
     # ---- parameter sets (payload bits by gen_avc.py) --------------------------------------------
     def sps(self):
@@ -473,6 +474,18 @@ class Synth:
                         for (w_, o_) in e["chroma"]:
                             bits = se(bits, w_)
                             bits = se(bits, o_)
+            elif self.wp_ends and ((st == 0 and self.wp) or (st == 1 and self.wbp == 1)):
+                bits = ue(bits, 7)  # luma_log2_weight_denom
+                bits = ue(bits, 7)  # chroma_log2_weight_denom
+                for lst in range(st + 1):
+                    for _ in range(hdr["nref0"] if lst == 0 else hdr["nref1"]):
+                        for planes in (1, 2):
+                            flag = r.random() < 0.5  # cleared: the default weight 128, offset 0
+                            bits = u(bits, 1, int(flag))
+                            if flag:
+                                for _p in range(planes):
+                                    bits = se(bits, r.choice([-128, 127, -128, 127, r.randint(-128, 127)]))
+                                    bits = se(bits, r.choice([-128, 127, 0, r.randint(-128, 127)]))
             elif (st == 0 and self.wp) or (st == 1 and self.wbp == 1):
                 ld, cd = r.randint(0, 6), r.randint(0, 6)
                 bits = ue(bits, ld)
@@ -676,6 +689,11 @@ STREAMS = [
                                                       pcm=0.0, cbp_zero=0.85)),
     ("cabac_hd1080_ibbp30", 120, 68, "I" + "PBB" * 9 + "PB", 72, dict(cabac=True, pcm=0.0, num_refs=2, level=4.0, crop=(0, 0, 0, 8), t8x8=True, scaling=True,
                                                                       weighted_bipred=2, skip=0.5, coef_density=0.10, intra_in_inter=0.02, cbp_zero=0.85)),
+    # explicit weights at the ends of pred_weight_table's ranges in P and B slices: denominator 7 (the default weight 128 beside explicit ones, the
+    # (a & b) == 128 pairs of bi-prediction), weights and offsets -128 / 127
+    ("weighted_denom7", 4, 3, "IPPBPBB", 85, dict(num_refs=2, weighted_pred=1, weighted_bipred=1, wp_ends=True, intra_in_inter=0.05, skip=0.1)),
+    ("cabac_weighted_denom7", 4, 3, "IPPBPBB", 86, dict(cabac=True, pcm=0.0, num_refs=2, weighted_pred=1, weighted_bipred=1, wp_ends=True,
+                                                         intra_in_inter=0.05, skip=0.1, t8x8=True)),
 ]
 
 

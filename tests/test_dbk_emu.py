@@ -11,6 +11,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
+from tests import edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -53,6 +54,8 @@ CASES = [
     # the copy-only path (dk_vcopy); with a few coded macroblocks the two paths alternate inside a group
     ("static", "IPP", 13, 10, dict(num_refs=1, mv_range=0, residual_prob=0.0, intra_in_inter=0.0)),
     ("static_some_coded", "IPPP", 12, 20, dict(num_refs=1, mv_range=0, residual_prob=0.04, intra_in_inter=0.01)),
+    # the ends of the QP, filter-offset, level and vector ranges (tests/edge_cases.py): indexA / indexB clamped at 0 and 51 around I_PCM
+    *[(f"edge_{n}", p, 6, 5, kw) for n, p, kw, _ in edge_cases.CASES if n.startswith(("filter", "level_ends", "mv_ends"))],
 ]
 
 

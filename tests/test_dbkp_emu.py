@@ -10,6 +10,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle
+from tests import edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALPHA = [0] * 16 + [4, 4, 5, 6, 7, 8, 9, 10, 12, 13, 15, 17, 20, 22, 25, 28, 32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255]
@@ -67,6 +68,8 @@ CASES = [
     ("tiny", "IPB", 1, 1, dict()),
     ("extreme_vectors", "IPBB", 8, 5, dict(mv_range=2047, num_refs=2, p_skip=0.0)),  # differences beyond int16: the packed compare must not wrap
     ("small_differences", "IPBB", 9, 6, dict(mv_range=3, num_refs=1, residual_prob=0.05)),  # |dx|, |dy| around the threshold of 4
+    # the ends of the QP, filter-offset and vector ranges (tests/edge_cases.py): alpha / beta / indexA at clamped indices, vectors at +-32768
+    *[(f"edge_{n}", p, 6, 5, kw) for n, p, kw, _ in edge_cases.CASES if n.startswith(("filter", "mv_ends"))],
 ]
 
 

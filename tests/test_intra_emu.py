@@ -11,6 +11,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
+from tests import edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -48,6 +49,12 @@ CASES = {
     "i_slices_qp": dict(gop="II", w=8, h=6, kw=dict(slices_per_frame=4, scaling=True)),
     "p_sparse_intra_wide": dict(gop="IPP", w=70, h=5, kw=dict(intra_in_inter=0.01)),  # rows and 64-macroblock chunks without any intra macroblock
     "i_8x8_qp_around_36": dict(gop="II", w=8, h=5, kw=dict(i_kinds=(P.MB_I8x8,), t8x8=True, scaling=True, qp_base=37)),  # both forms of the 8x8 dequantisation
+    # the ends of the scaling and level ranges (tests/edge_cases.py), intra macroblocks of I pictures and of P / B pictures
+    **{f"edge_{n}": dict(gop=p, w=6, h=5, kw=dict(kw, intra_in_inter=0.3)) for n, p, kw, _ in edge_cases.CASES
+       if n.startswith(("scaling", "level_ends", "filter_qp0"))},
+    "edge_scaling4_qp48_i16": dict(gop="I", w=6, h=5, kw=dict(i_kinds=(P.MB_I16x16,), scaling=True, scaling_range=(1, 256), qp_base=50, stress=True)),
+    "edge_level_ends_all_i": dict(gop="II", w=7, h=4, kw=dict(level_ends=True, i_kinds=(P.MB_I4x4, P.MB_I8x8, P.MB_I16x16), t8x8=True, scaling=True,
+                                                               scaling_range=(150, 256), qp_base=48, stress=True)),
 }
 
 

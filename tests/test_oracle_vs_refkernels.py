@@ -10,6 +10,7 @@ import pytest
 
 from edge264_amd import packet as P
 from edge264_amd import synth
+from tests import edge_cases
 
 W, H = 6, 5
 ALL_I = (P.MB_I8x8, P.MB_I4x4, P.MB_I16x16)
@@ -34,7 +35,7 @@ CASES = [
 ]
 
 
-def run_stream(oracle, refkernels, seed, pattern, kw, w=W, h=H):
+def run_stream(oracle, refkernels, seed, pattern, kw, w=W, h=H, seen=None):
     s = synth.StreamSynth(w, h, seed, **kw)
     nb = P.frame_bytes(w, h) + 16
     rng = np.random.default_rng(seed + 1000)
@@ -44,6 +45,8 @@ def run_stream(oracle, refkernels, seed, pattern, kw, w=W, h=H):
     for i, t in enumerate(pattern):
         pkt = s.next_frame(t)
         d = int(P.Packet(pkt).hdr["dst_slot"])
+        if seen is not None:
+            seen.update(edge_cases.census(pkt))
         for passes in (1, 2):  # reconstruction, then deblocking: compared after each
             oracle.decode_frame(pkt, dpb_o, passes)
             refkernels.replay(pkt, dpb_r, w, h, passes)
@@ -95,3 +98,24 @@ def test_odd_geometry(oracle, refkernels):
             run_stream(oracle, refkernels, 7, "IPB", dict(t8x8=True, i_kinds=ALL_I, mv_range=100), w, h)
     finally:
         refkernels.lib.ref_force_4x4_calls(0)
+
+
+@pytest.mark.parametrize("name,pattern,kw,must", edge_cases.CASES, ids=[c[0] for c in edge_cases.CASES])
+def test_range_ends(oracle, refkernels, name, pattern, kw, must):
+    """The values at the ends of what a packet may carry (tests/edge_cases.py): weight denominators 0..7, the default weight 128 of
+    denominator 7 and the (a & b) == 128 pairs, weights / offsets -128 / 127, scaling entries up to 255 at QP 48..51, int16 and byte-form
+    level ends, vectors at +-32768, indexA / indexB clamped by offsets of +-12 at QP 0 and 51 around I_PCM."""
+    from collections import Counter
+    seen = Counter()
+    for seed in range(4):
+        run_stream(oracle, refkernels, seed, pattern, kw, seen=seen)
+    assert all(seen[k] for k in must), {k: seen[k] for k in must}
+
+
+def test_range_ends_wide(oracle, refkernels):
+    """Vectors at the int16 ends on a picture 1920 samples wide, weights at denominator 7: the edge-emulation clamp far from both sides."""
+    from collections import Counter
+    seen = Counter()
+    run_stream(oracle, refkernels, 9, "IPBP", dict(mv_ends=0.3, weighted=1, weight_denoms=[(7, 7)], weight_pins=0.3, t8x8=True,
+                                                    i_kinds=ALL_I), 120, 3, seen=seen)
+    assert seen["mv_ends"] and seen["denom7_default"] and seen["bipred_and128"], seen

@@ -6,11 +6,13 @@ reference's error convention (positive errno, README.md:188-209), never a fault.
 import errno
 import glob
 import os
+from collections import Counter
 
 import numpy as np
 import pytest
 
 from edge264_amd import backend, packet as P, synth
+from tests import edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 STREAMS = os.path.join(HERE, "golden", "streams")
@@ -159,3 +161,32 @@ def test_byte_fuzz_never_faults(gop):
         for _ in range(int(rng.integers(1, 6))):
             buf[int(rng.integers(0, limit))] = int(rng.integers(0, 256))
         assert backend.packet_check(bytes(buf)) in (0, errno.EINVAL)
+
+
+@pytest.mark.parametrize("name,pattern,kw,must", edge_cases.CASES, ids=[c[0] for c in edge_cases.CASES])
+def test_range_end_packets_pass(name, pattern, kw, must):
+    """packets at the ends of the weight, scaling, level and vector ranges (tests/edge_cases.py) are legal: the validator accepts them in both
+    forms, they hold the edge they are named after, and the wire form carries it unchanged"""
+    seen = Counter()
+    for seed in range(2):
+        for raw in synth.StreamSynth(6, 5, seed, **kw).gop(pattern):
+            c = edge_cases.census(raw)
+            wire = backend.packet_compact(raw)
+            assert backend.packet_check(raw) == 0 and backend.packet_check(wire) == 0
+            assert edge_cases.census(wire) == c
+            seen.update(c)
+    assert all(seen[k] for k in must), {k: seen[k] for k in must}
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(REF), "..", "edge264_amd", "libedge264_hipfront.so")), reason="front end not built")
+@pytest.mark.parametrize("name", ["weighted_denom7", "cabac_weighted_denom7"])
+def test_denominator_7_fixtures_reach_the_edges(oracle, name):
+    """the pred_weight_table fixtures at the ends of their ranges, through the real front end: denominator 7 with its default weight 128 in use,
+    the (a & b) == 128 pairs, a default beside an explicit weight, weights and offsets -128 / 127, in P and B slices"""
+    from oracle.pyoracle import HipFront
+    _, _, packets = HipFront().decode_capture(open(os.path.join(STREAMS, name + ".264"), "rb").read(), oracle)
+    seen = edge_cases.stream_census(packets)
+    assert all(seen[k] for k in ("luma_denom7", "chroma_denom7", "denom7_default", "bipred_and128", "default_beside_explicit", "offset_ends",
+                                 "weight_ends")), seen
+    types = {int(s["slice_type"]) for p in packets for s in P.Packet(p).slices if s["luma_log2_weight_denom"] == 7}
+    assert {0, 1} <= types, types

@@ -11,6 +11,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
+from tests import edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -53,6 +54,9 @@ CASES = {
     "all_residual": dict(gop="IPP", w=6, h=4, kw=dict(residual_prob=1.0, p_skip=0.0)),
     # QP walks around 36: lanes of one wave on both sides of the 8x8 dequantisation's two forms (residual.c:214-247; one flow since round 4)
     "t8x8_qp_around_36": dict(gop="IPB", w=9, h=6, kw=dict(t8x8=True, scaling=True, residual_prob=1.0, qp_base=37)),
+    # the ends of the weight, scaling, level and vector ranges (tests/edge_cases.py)
+    **{f"edge_{n}": dict(gop=p, w=6, h=5, kw=kw) for n, p, kw, _ in edge_cases.CASES if set(p) - {"I"}},
+    "edge_mv_ends_wide": dict(gop="IPBP", w=37, h=3, kw=dict(mv_ends=0.3, weighted=1, weight_denoms=[(7, 7)], weight_pins=0.3, p_skip=0.5)),
 }
 
 

@@ -2,7 +2,8 @@
 """tools/emu_sweep.py -- CHECKING TOOL (CPU): a randomised differential run of the four kernels' own source (tests/emu: the host build of
 edge264_amd/csrc/e264_{dbkp,pred,intra,dbk}.h) against the oracle, whole pipeline per picture -- parameters, prediction + residual, intra, deblocking --
 on synthetic streams whose every option is drawn from the seed: picture size (1 x 1 ... 26 x 14 macroblocks), GOP shape, references, weighting
-scheme, transforms, scaling lists, QP, residual density, PCM, intra share, slices per picture, far vectors, filter offsets, deblocking idc.
+scheme, transforms, scaling lists, QP, residual density, PCM, intra share, slices per picture, far vectors, filter offsets, deblocking idc, and
+the ends of the weight, scaling, level, vector and chroma QP offset ranges (synth.range_end_options).
 The tests run fixed cases; this is for leaving a few CPU-hours on it.
 
     python tools/emu_sweep.py [--seeds A:B] [--split 0|1]      prints one line per mismatch and a summary
@@ -36,6 +37,9 @@ def options(seed):
         kw["i_kinds"] = (P.MB_I4x4, P.MB_I16x16, P.MB_I8x8) if kw["t8x8"] else (P.MB_I4x4,)
     kw["slices_per_frame"] = min(kw["slices_per_frame"], w * h)
     kw["n_slots"] = max(6, kw["num_refs"] + 3)
+    kw.update(synth.range_end_options(r))
+    if r.random() < 0.2:  # indexA / indexB clamped at 0 and 51
+        kw["filter_offsets"] = (int(r.choice([-12, 12])), int(r.choice([-12, 12])))
     return w, h, gop, kw
 
 

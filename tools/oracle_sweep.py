@@ -2,7 +2,8 @@
 """tools/oracle_sweep.py -- CHECKING TOOL (CPU; needs oracle/_ref/libe264_refkernels.so, i.e. the build container or its prebuilt library): the ORACLE against
 the reference's own static kernels (src/edge264_{intra,inter,residual,deblock}.c behind oracle/ref_kernels_harness.c) on synthetic packets whose every
 generator option is drawn from the seed -- what no bitstream writer here can produce is in reach this way: vectors hundreds of samples outside the picture,
-16 references, explicit weights at the ends of their ranges, QP 0..51, every transform / scaling-list / slice / deblocking combination.  Compared after the
+16 references, explicit weights at the ends of their ranges (denominators 0..7, the default 128, -128 / 127; synth.range_end_options), scaling entries up
+to 255, int16 and byte-form level ends, vectors at +-32768, QP 0..51, filter and chroma QP offsets of +-12, every transform / scaling-list / slice / deblocking combination.  Compared after the
 reconstruction pass and after the deblocking pass.  tests/test_oracle_vs_refkernels.py holds the fixed cases.
 
     python tools/oracle_sweep.py [--seeds A:B]
@@ -34,6 +35,7 @@ def options(seed):
     if kw["t8x8"] and r.random() < 0.5:
         kw["i_kinds"] = (P.MB_I8x8, P.MB_I4x4, P.MB_I16x16)
     kw["slices_per_frame"] = min(kw["slices_per_frame"], w * h)
+    kw.update(synth.range_end_options(r))
     return w, h, gop, kw
 
 
