@@ -29,6 +29,12 @@ roofline (all per submission of one frame of every stream of one GPU; DESIGN.md 
                         on the configuration), else null.
 cpu_baseline: the unmodified reference decoder on the host cores (oracle/cpu_baseline.py), plus the reference's own SIMD
 kernels replaying the bench packets on one core (`kernel_replay`).
+
+A plain run does what the headline needs and no more: it builds the synthetic GOPs (one worker process per GOP, while this
+process sets up the device), uploads them, warms up, times the steps, writes --dump-outputs and prints the line, roofline
+included (its kernel times are taken live in the timed steps, its counters come from files).  `--full` adds the rest:
+`verify` / `bit_exact` (every stream and frame of one more GOP against the CPU oracle), `cpu_baseline`, `other_configs`,
+`staggered_gops`, `same_input`, `system`, `pcie_inclusive` and `single_stream`; in a plain line these keys are null.
 """
 import argparse
 import json
@@ -49,6 +55,8 @@ SIDE_QUEUE_DEFAULT = 0
 DBK_BYTES = 144  # deblocking parameters per macroblock (edge264_amd/csrc/e264_kernels.h)
 DUMP_BYTES = 64 * 10**6  # --dump-outputs: both arrays together, headers included
 DUMP_SEED = 2024  # --dump-outputs: the sample positions of stream k come from default_rng((DUMP_SEED, k))
+# what only --full runs: a plain run is the headline alone (set up, warm up, time the steps, --dump-outputs, the line)
+FULL_ONLY = ("no_verify", "no_cpu_baseline", "no_other_configs", "no_host_packets", "no_system", "no_staggered", "no_single_stream", "no_same_input")
 
 
 def parse_args(argv=None):
@@ -82,9 +90,15 @@ def parse_args(argv=None):
                     "so that the kernels are timed on real motion / partition statistics (tools/make_capture.py writes one from a .264)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the pictures the last timed step left in "
                     "rank 0's streams to DIR/pictures.npy and DIR/positions.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run everything else the line can carry: the oracle check of every stream "
+                    "and frame, the CPU baseline, the other configurations and the PCIe-inclusive, staggered, same-input, system and single-stream legs "
+                    "(the --no-* options leave parts out); without it those keys are null")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        for flag in FULL_ONLY:
+            setattr(args, flag, True)
     return args
 
 
@@ -589,6 +603,14 @@ def dump_outputs(out_dir, streams, parsed, frame_nb):
     np.save(os.path.join(out_dir, "positions.npy"), positions)
 
 
+def synth_gop(W, H, seed, kw, gop):
+    """One synthetic GOP and the traffic model of each of its packets.  Runs in a worker process: a 1080p GOP is seconds of pure Python,
+    and the GOPs of the variants are independent of each other and of the device's set-up."""
+    from edge264_amd import packet as P, synth
+    packets = synth.StreamSynth(W, H, seed=seed, **kw).gop(gop)
+    return packets, [P.Packet(p).traffic_model() for p in packets]
+
+
 def main() -> int:
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -607,6 +629,44 @@ def main() -> int:
     if args.gpus is not None and args.gpus != world:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: refusing to report a number for the wrong GPU count", file=sys.stderr)
         return 2
+    # weak scaling (default): rank r owns streams shard_streams(streams * world, r, world) (= `streams` of them);
+    # --total-streams / --config5: the job's streams are fixed and sharded (strong scaling)
+    strong = args.total_streams is not None
+    my_streams = len(shard_streams(args.total_streams if strong else args.streams * world, rank, world))
+    if my_streams == 0:
+        print(f"bench.py: rank {rank} of {world} has no stream to decode (--total-streams {args.total_streams})", file=sys.stderr)
+        return 2
+
+    from edge264_amd import packet as P, synth
+
+    W, H = args.width_mbs, args.height_mbs
+    ALL_I = (P.MB_I4x4, P.MB_I8x8, P.MB_I16x16)
+    head_i = tuple(k for k, n in zip(ALL_I, ("4", "8", "16")) if n in os.environ.get("E264_I_KINDS", "4,8,16").split(","))  # measuring aid: intra kinds of the synthetic GOP
+    fill_value = 128
+    if args.capture:
+        # ---- captured packets of a real bitstream (reference front end -> our emitters), first stream of the file ----
+        from edge264_amd import replay
+        cap = replay.Capture.load(args.capture)
+        packets = cap.of_stream(cap.stream_ids()[0])
+        parsed = [P.Packet(p) for p in packets]
+        W, H = int(parsed[0].hdr["width_mbs"]), int(parsed[0].hdr["height_mbs"])
+        args.gop = f"capture:{os.path.basename(args.capture)}:{len(packets)} pictures"
+        fill_value = 0
+        args.no_other_configs = True
+    else:
+        # ---- synthetic input (same bytes on every rank: seeded) -------------------------------
+        skw = dict(t8x8=True, i_kinds=head_i, num_refs=2, residual_prob=float(os.environ.get("E264_RESIDUAL_PROB", 0.3)))
+        skw.update(json.loads(os.environ.get("E264_SYNTH_KW", "{}")))  # measuring aid (tools/visits/gpu_sweep.sh): what each kernel's time depends on
+        # one worker process per GOP, started before this process imports torch and opens the device, which it does meanwhile;
+        # spawned, not forked: the workers start from a fresh interpreter and never touch the GPU
+        import concurrent.futures
+        import multiprocessing
+        n_var = max(1, args.variants)
+        pool = concurrent.futures.ProcessPoolExecutor(max_workers=min(n_var, len(os.sched_getaffinity(0))), mp_context=multiprocessing.get_context("spawn"))
+        gop_jobs = [pool.submit(synth_gop, W, H, 1234 + v, skw, args.gop) for v in range(n_var)]
+    # a run with any of the measuring aids set does not measure BASELINE configs[2] any more: the line says so (config.synth_overrides, workload)
+    synth_overrides = {k: os.environ[k] for k in ("E264_I_KINDS", "E264_RESIDUAL_PROB", "E264_SYNTH_KW") if os.environ.get(k) and not args.capture}
+
     import importlib
     backend = importlib.import_module(os.environ.get("E264_BENCH_BACKEND", "edge264_amd.backend"))  # tests: a stub device on CPU ranks
     stub = getattr(backend, "IS_STUB", False)
@@ -640,52 +700,6 @@ def main() -> int:
                 os.sched_setaffinity(0, self.bound)
             return False
 
-    from edge264_amd import packet as P, synth
-
-    W, H = args.width_mbs, args.height_mbs
-    ALL_I = (P.MB_I4x4, P.MB_I8x8, P.MB_I16x16)
-    head_i = tuple(k for k, n in zip(ALL_I, ("4", "8", "16")) if n in os.environ.get("E264_I_KINDS", "4,8,16").split(","))  # measuring aid: intra kinds of the synthetic GOP
-    fill_value = 128
-    if args.capture:
-        # ---- captured packets of a real bitstream (reference front end -> our emitters), first stream of the file ----
-        from edge264_amd import replay
-        cap = replay.Capture.load(args.capture)
-        packets = cap.of_stream(cap.stream_ids()[0])
-        parsed = [P.Packet(p) for p in packets]
-        W, H = int(parsed[0].hdr["width_mbs"]), int(parsed[0].hdr["height_mbs"])
-        args.gop = f"capture:{os.path.basename(args.capture)}:{len(packets)} pictures"
-        fill_value = 0
-        args.no_other_configs = True
-    else:
-        # ---- synthetic input (same bytes on every rank: seeded) -------------------------------
-        skw = dict(t8x8=True, i_kinds=head_i, num_refs=2, residual_prob=float(os.environ.get("E264_RESIDUAL_PROB", 0.3)))
-        skw.update(json.loads(os.environ.get("E264_SYNTH_KW", "{}")))  # measuring aid (tools/visits/gpu_sweep.sh): what each kernel's time depends on
-    # a run with any of the measuring aids set does not measure BASELINE configs[2] any more: the line says so (config.synth_overrides, workload)
-    synth_overrides = {k: os.environ[k] for k in ("E264_I_KINDS", "E264_RESIDUAL_PROB", "E264_SYNTH_KW") if os.environ.get(k) and not args.capture}
-    if not args.capture:
-        vpk = [synth.StreamSynth(W, H, seed=1234 + v, **skw).gop(args.gop) for v in range(max(1, args.variants))]
-        packets = vpk[0]
-        parsed = [P.Packet(p) for p in packets]
-    if args.capture:
-        vpk = [packets]
-    V = len(vpk)
-    vparsed = [[P.Packet(p) for p in pk] for pk in vpk]
-    for vp in vparsed:  # the variants differ in content only: same slots, same geometry
-        assert [int(q.hdr["dst_slot"]) for q in vp] == [int(q.hdr["dst_slot"]) for q in parsed]
-    models = [pk.traffic_model() for vp in vparsed for pk in vp]
-    used = 0
-    for pk in (q for vp in vparsed for q in vp):
-        used |= 1 << int(pk.hdr["dst_slot"]) | int(pk.hdr["ref_slots"])
-    n_slots = max(used.bit_length(), 3)
-    frame_nb = int(parsed[0].hdr["plane_size_Y"]) + int(parsed[0].hdr["plane_size_C"])
-
-    # weak scaling (default): rank r owns streams shard_streams(streams * world, r, world) (= `streams` of them);
-    # --total-streams / --config5: the job's streams are fixed and sharded (strong scaling)
-    strong = args.total_streams is not None
-    my_streams = len(shard_streams(args.total_streams if strong else args.streams * world, rank, world))
-    if my_streams == 0:
-        print(f"bench.py: rank {rank} of {world} has no stream to decode (--total-streams {args.total_streams})", file=sys.stderr)
-        return 2
     dev = backend.Device(local_rank)
     dev.set_option("waves", args.waves)
     if args.intra_waves:
@@ -693,6 +707,27 @@ def main() -> int:
     side_queue = int(os.environ.get("E264_SIDE_QUEUE", SIDE_QUEUE_DEFAULT))  # 0: one queue; 1: parameter kernel beside the prediction kernel; 2: beside the intra kernel
     dev.set_option("side_queue", side_queue)
     dev.set_option("upload_queue", int(os.environ.get("E264_UPLOAD_QUEUE", 1)))
+
+    if args.capture:
+        vpk = [packets]
+        models = [pk.traffic_model() for pk in parsed]
+    else:
+        gops = [job.result() for job in gop_jobs]
+        pool.shutdown()
+        vpk = [pk for pk, _ in gops]
+        models = [m for _, ms in gops for m in ms]
+        packets = vpk[0]
+        parsed = [P.Packet(p) for p in packets]
+    V = len(vpk)
+    vparsed = [[P.Packet(p) for p in pk] for pk in vpk]
+    for vp in vparsed:  # the variants differ in content only: same slots, same geometry
+        assert [int(q.hdr["dst_slot"]) for q in vp] == [int(q.hdr["dst_slot"]) for q in parsed]
+    used = 0
+    for pk in (q for vp in vparsed for q in vp):
+        used |= 1 << int(pk.hdr["dst_slot"]) | int(pk.hdr["ref_slots"])
+    n_slots = max(used.bit_length(), 3)
+    frame_nb = int(parsed[0].hdr["plane_size_Y"]) + int(parsed[0].hdr["plane_size_C"])
+
     streams, dpk = [], []
     for s in range(my_streams):
         st = backend.Stream(dev, W, H)
@@ -1018,7 +1053,7 @@ def main() -> int:
         out = {
             "metric": "1080p frames/s/GPU (bit-exact YUV) + achieved HBM GB/s vs 8 TB/s peak",
             "value": round(value, 1), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": "u8", "data": "captured bitstream packets" if args.capture else "synthetic",

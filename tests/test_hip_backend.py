@@ -233,7 +233,7 @@ def test_bench_distributed_path_on_one_gpu():
         port = sk.getsockname()[1]
     env = dict(os.environ, E264_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--streams", "4", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--streams", "4", "--full", "--no-cpu-baseline",
                         "--no-other-configs", "--no-host-packets", "--no-same-input"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -260,7 +260,7 @@ def test_bench_dump_outputs_are_the_decoded_pictures(tmp_path):
     env.pop("WORLD_SIZE", None)
     w, h, gop, n_streams, n_var = 20, 6, "IPPP", 3, 2
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--streams", str(n_streams), "--gop", gop,
-                        "--width-mbs", str(w), "--height-mbs", str(h), "--variants", str(n_var), "--no-cpu-baseline", "--no-other-configs",
+                        "--width-mbs", str(w), "--height-mbs", str(h), "--variants", str(n_var), "--full", "--no-cpu-baseline", "--no-other-configs",
                         "--no-host-packets", "--no-system", "--no-staggered", "--no-single-stream", "--no-same-input",
                         "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

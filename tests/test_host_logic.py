@@ -335,6 +335,28 @@ def test_bench_says_when_the_synthetic_content_is_overridden():
             assert "2 distinct GOPs" in d["config"]["workload"]
 
 
+def test_bench_runs_the_other_legs_only_with_full():
+    """A plain bench.py run is the headline alone: every part a --full run adds (the oracle check, the CPU baseline, the other configurations,
+    the PCIe-inclusive, staggered, same-input, system and single-stream legs) is switched off, and the line says `full: false`.  --full
+    switches them on again; a --no-* option still leaves its part out of a full run."""
+    import json
+    import bench
+    plain = bench.parse_args([])
+    assert plain.full is False and all(getattr(plain, f) is True for f in bench.FULL_ONLY)
+    full = bench.parse_args(["--full", "--no-system"])
+    assert full.full is True and full.no_system is True
+    assert all(getattr(full, f) is False for f in bench.FULL_ONLY if f != "no_system")
+    env = dict(os.environ, E264_BENCH_BACKEND="tests.stub_backend", OMP_NUM_THREADS="1", PYTHONPATH=ROOT)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--streams", "2", "--gop", "IP", "--width-mbs", "4", "--height-mbs", "3"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["full"] is False and d["value"] > 0
+    for k in ("verify", "bit_exact", "cpu_baseline", "other_configs", "staggered_gops", "pcie_inclusive", "same_input", "system", "single_stream"):
+        assert k in d and d[k] is None, k
+
+
 def test_bench_dump_outputs_is_sampled_within_budget_and_repeatable(tmp_path):
     """--dump-outputs DIR (stub device, whose pictures are the fill value): 1080p pictures of 8 streams do not fit into 64 MB, so every
     picture is sampled; the arrays are float32 / float64, stay within the budget, and a second run with the same arguments writes the

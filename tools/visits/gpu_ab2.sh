@@ -10,7 +10,7 @@ try:
     print(sys.argv[2], d['value'], d['bit_exact'], {k.split('_')[1]:v['ms_per_launch'] for k,v in d['roofline']['kernels'].items()}, [(k[:10], v['value'], v['bit_exact']) for k,v in o.items()])
 except Exception as e:
     print(sys.argv[2], 'FAILED', e)" $1 $2; }
-B="python bench.py --no-cpu-baseline --no-host-packets --no-same-input --steps 8 --warmup 2 $BENCH_ARGS"
+B="python bench.py --full --no-cpu-baseline --no-host-packets --no-same-input --steps 8 --warmup 2 $BENCH_ARGS"
 timeout 300 $B > $OUT/bench_main.json 2> $OUT/bench_main.err; summ $OUT/bench_main.json main
 for lib in $(ls edge264_amd/variants/*.so 2>/dev/null); do
   n=$(basename $lib .so)

@@ -6,12 +6,12 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 600 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/pytest_gpu.log
-timeout 300 python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
+timeout 300 python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
 cd /tmp
 for c in RD WR; do
   if [ $c = RD ]; then CTRS="TCC_EA0_RDREQ TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B"; else CTRS="TCC_EA0_WRREQ TCC_EA0_WRREQ_64B TCC_EA0_WRREQ_DRAM"; fi
   timeout 300 rocprofv3 --pmc $CTRS -d $OUT/calib_$c -- $REPO/tools/calib/pmc_calib > $OUT/calib_$c.log 2>&1; echo "calib $c rc=$?"
-  timeout 400 rocprofv3 --pmc $CTRS -d $OUT/bench_$c -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify > $OUT/bench_$c.log 2>&1; echo "bench $c rc=$?"
+  timeout 400 rocprofv3 --pmc $CTRS -d $OUT/bench_$c -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-verify > $OUT/bench_$c.log 2>&1; echo "bench $c rc=$?"
 done
 timeout 300 rocprofv3 --kernel-trace -d $OUT/calib_kt -- $REPO/tools/calib/pmc_calib > $OUT/calib_kt.log 2>&1
 cd $REPO

@@ -5,7 +5,7 @@
 TAG=${1:-pmci}
 REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-B="python $REPO/bench.py --gop II --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-other-configs --no-host-packets"
+B="python $REPO/bench.py --full --gop II --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-other-configs --no-host-packets"
 cd /tmp
 for lib in main $(ls $REPO/edge264_amd/variants/*.so 2>/dev/null); do
   n=$(basename $lib .so); env=""

@@ -14,7 +14,7 @@ timeout 400 rocprofv3 --pmc TCC_EA0_RDREQ TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TC
 timeout 400 rocprofv3 --pmc TCC_EA0_WRREQ TCC_EA0_WRREQ_64B -d $OUT/pmc_wr -- $B --steps 1 --warmup 0 > /dev/null 2> $OUT/pmc_wr.err; echo "wr rc=$?"
 timeout 400 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM -d $OUT/pmc_sq -- $B --steps 1 --warmup 0 > /dev/null 2> $OUT/pmc_sq.err; echo "sq rc=$?"
 # the host-packet legs alone (page-locked packets, version 4 and wire form): e264_expand_kernel's duration beside the four
-timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_wire -- python $REPO/bench.py --no-cpu-baseline --no-verify --no-other-configs --no-same-input --no-system --no-single-stream --no-staggered > $OUT/bench_wire_kt.json 2> $OUT/bench_wire_kt.err; echo "wire kt rc=$?"
+timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_wire -- python $REPO/bench.py --full --no-cpu-baseline --no-verify --no-other-configs --no-same-input --no-system --no-single-stream --no-staggered > $OUT/bench_wire_kt.json 2> $OUT/bench_wire_kt.err; echo "wire kt rc=$?"
 cd $REPO
 python tools/rocprof_summary.py $(find $OUT/prof_kt -name '*.db' | head -1) > $OUT/kernel_stats.txt 2>&1; cat $OUT/kernel_stats.txt
 python tools/rocprof_summary.py $(find $OUT/prof_wire -name '*.db' | head -1) > $OUT/kernel_stats_host_packets.txt 2>&1; cat $OUT/kernel_stats_host_packets.txt
@@ -22,7 +22,7 @@ python tools/pmc_summary.py $(find $OUT/pmc_rd $OUT/pmc_wr -name '*.db') --traff
 python tools/pmc_summary.py $(find $OUT/pmc_sq -name '*.db') --sq-json $OUT/sq_mix.json --streams 256 --gop IPPPPPPP --bench-json $OUT/bench_kt.json > $OUT/pmc_sq_instruction_mix.txt 2>&1
 # the line of record AFTER the counters: it quotes the traffic / SQ files of this very build
 cp $OUT/hbm_traffic.json profiles/r06_hbm_traffic.json; cp $OUT/sq_mix.json profiles/r06_sq_mix.json
-T0=$(date +%s); timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$? seconds=$(( $(date +%s) - T0 ))"
+T0=$(date +%s); timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$? seconds=$(( $(date +%s) - T0 ))"
 for NS in 512 1024; do
   timeout 300 $B --streams $NS --steps 3 > $OUT/bench_streams$NS.json 2> $OUT/bench_streams$NS.err
   python -c "

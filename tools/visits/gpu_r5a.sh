@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 120 tools/calib/mfma_tap > $OUT/mfma_tap.txt 2>&1; echo "mfma_tap rc=$?"; cat $OUT/mfma_tap.txt
-timeout 400 python bench.py --no-cpu-baseline --no-host-packets > $OUT/bench_main.json 2> $OUT/bench_main.err; echo "bench rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-host-packets > $OUT/bench_main.json 2> $OUT/bench_main.err; echo "bench rc=$?"
 python -c "
 import json,sys
 d=json.load(open('$OUT/bench_main.json')); o=d.get('other_configs') or {}

@@ -7,7 +7,7 @@ REPO=$(pwd)
 for v in $2; do
   lib=$REPO/edge264_amd/variants/libedge264_hip_$v.so
   [ $v = main ] && lib=$REPO/edge264_amd/libedge264_hip.so
-  E264_ALLOW_ABLATION=1 E264_HIP_LIB=$lib timeout 400 python bench.py --no-cpu-baseline --no-host-packets --no-other-configs --no-system $BENCH_ARGS > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  E264_ALLOW_ABLATION=1 E264_HIP_LIB=$lib timeout 400 python bench.py --full --no-cpu-baseline --no-host-packets --no-other-configs --no-system $BENCH_ARGS > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   python -c "
 import json,sys
 d=json.load(open('$OUT/bench_$v.json'))

@@ -1,6 +1,6 @@
 # what each kernel's time depends on: the bench GOP with one property of the synthetic content changed at a time (E264_SYNTH_KW)
 mkdir -p gpurun_out/sweep
-B="python bench.py --no-cpu-baseline --no-other-configs --no-host-packets --no-same-input --variants 1 --steps 6 --warmup 2"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-host-packets --no-same-input --variants 1 --steps 6 --warmup 2"
 i=0
 while read -r KW; do
   i=$((i+1))
