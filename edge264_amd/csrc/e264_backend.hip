@@ -745,7 +745,9 @@ static int check_packet_deep(const void *packet, size_t bytes, uint8_t *const *s
 		return fail(EINVAL, "strides");
 	if ((uint64_t)h->plane_size_Y < (uint64_t)h->stride_Y * h->height_mbs * 16 || (uint64_t)h->plane_size_C < (uint64_t)h->stride_C * h->height_mbs * 8)
 		return fail(EINVAL, "plane sizes");
+	if (h->plane_size_Y & 15) return fail(EINVAL, "plane_size_Y alignment"); // chroma rows keep the 8 / 4-byte alignment of stride_C
 	const uint64_t frame_need = (uint64_t)h->plane_size_Y + h->plane_size_C;
+	if (frame_need >= 1ull << 31) return fail(EINVAL, "picture of 2 GiB or more"); // (the kernels' slot offsets are 32-bit)
 	if (slots && slot_bytes && slots[dst] && frame_need > slot_bytes[dst]) return fail(EINVAL, "picture larger than the destination slot");
 	const uint8_t *mot = h->motion_off ? p + h->motion_off : nullptr; // compact motion records, up to payload_off
 	const uint32_t mot_bytes = h->motion_off ? h->payload_off - h->motion_off : 0;

@@ -86,10 +86,14 @@ typedef struct E264FrameHdr { /* 80 bytes */
 	uint32_t total_bytes;     /* whole packet */
 	uint16_t width_mbs;
 	uint16_t height_mbs;
-	uint32_t stride_Y;        /* bytes between luma rows (src/edge264_headers.c:2032) */
-	uint32_t stride_C;        /* bytes between chroma rows; a row is [Cb | Cr], Cr = Cb + stride_C/2 (:2041, :182) */
-	uint32_t plane_size_Y;
-	uint32_t plane_size_C;
+	uint32_t stride_Y;        /* bytes between luma rows (src/edge264_headers.c:2032): a multiple of 16, at least 16 * width_mbs */
+	uint32_t stride_C;        /* bytes between chroma rows; a row is [Cb | Cr], Cr = Cb + stride_C/2 (:2041, :182): a multiple of 8, at
+	                             least 16 * width_mbs (Cb rows are 8-byte aligned, Cr rows 4-byte aligned) */
+	uint32_t plane_size_Y;    /* bytes from the slot's start to Cb: a multiple of 16 (chroma rows keep the alignment of stride_C), at least
+	                             stride_Y * 16 * height_mbs */
+	uint32_t plane_size_C;    /* at least stride_C * 8 * height_mbs; plane_size_Y + plane_size_C < 2^31 (the kernels address a slot with
+	                             32-bit offsets).  The bytes of a slot that are not samples -- the padding right of each row, the gaps
+	                             behind each plane -- are never written, and no sample depends on them. */
 	uint32_t n_slices;
 	uint32_t slices_off;
 	uint32_t mbs_off;

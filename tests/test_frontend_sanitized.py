@@ -35,3 +35,15 @@ def test_validated_packets_keep_the_kernels_in_bounds():
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
     assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang++") or not os.path.exists(os.path.join(ROOT, "edge264_amd", "libedge264_hip.so")),
+                    reason="needs the ROCm clang (ASan runtime) and the built back end (its host-side packet validation)")
+def test_padded_layouts_keep_the_kernels_in_bounds():
+    """tools/sanitize/kernel_fuzz.py --layouts: the same packets, undamaged, in every layout of tests/layouts.py (padding right of the rows,
+    gaps behind the planes, a wide canvas) and both packet forms, through the kernels' source under AddressSanitizer on slots of exactly
+    plane_size_Y + plane_size_C + 64 bytes (e264hip_frame_alloc)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sanitize", "kernel_fuzz.py"), "--layouts", "--stride", "12"],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+    assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")

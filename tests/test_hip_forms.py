@@ -183,17 +183,22 @@ def run_batch(dev, oracle, how, decs, v4s, cfg, sent=None, max_lane=0, label="")
     for k, (d, p) in enumerate(zip(decs, v4s)):
         d.check(oracle, p, f"{label} picture {k} of {len(decs)} ({how})")
     got = observed(dev)
+    want = expected_submission(dev, how, v4s, sent, cfg, max_lane)
+    assert got == want, f"{label} ({how}): launched {got}, the rules say {want}"
+    return got
+
+
+def expected_submission(dev, how, v4s, sent, cfg, max_lane=0):
+    """the forms one submission of v4s (sent: the bytes submitted) must launch, by entry point"""
     cus = dev.launch_counts()["n_cus"]
     wire = [s[4] == P.E264_VERSION_COMPACT for s in sent]
     if how == "single":  # (one launch per picture)
         want = Counter()
         for p, s, x in zip(v4s, sent, wire):
             want.update(expected_forms([packet_info(p, s, how)], cfg, cus, max_lane, int(x)))
-        want = dict(want)
-    else:  # (resident packets are unfolded at upload)
-        want = expected_forms([packet_info(p, s, how) for p, s in zip(v4s, sent)], cfg, cus, max_lane, len(sent) if how != "resident" and any(wire) else 0)
-    assert got == want, f"{label} ({how}): launched {got}, the rules say {want}"
-    return got
+        return dict(want)
+    # (resident packets are unfolded at upload)
+    return expected_forms([packet_info(p, s, how) for p, s in zip(v4s, sent)], cfg, cus, max_lane, len(sent) if how != "resident" and any(wire) else 0)
 
 
 def n_cus(dev):

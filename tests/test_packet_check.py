@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from edge264_amd import backend, packet as P, synth
-from tests import edge_cases
+from tests import edge_cases, layouts
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 STREAMS = os.path.join(HERE, "golden", "streams")
@@ -190,3 +190,72 @@ def test_denominator_7_fixtures_reach_the_edges(oracle, name):
                                  "weight_ends")), seen
     types = {int(s["slice_type"]) for p in packets for s in P.Packet(p).slices if s["luma_log2_weight_denom"] == 7}
     assert {0, 1} <= types, types
+
+
+# ---- the layouts the gate accepts (include/edge264_cmd.h, E264FrameHdr.stride_Y .. plane_size_C) ---------------------------------------------
+
+def _geom(raw, over):
+    """raw with its four layout fields set to the tight layout's updated by over(tight header fields)"""
+    g = layouts.hdr_of(raw)
+    g.update(over(g))
+    buf = bytearray(raw)
+    h = np.frombuffer(buf, P.FRAME_HDR, 1)
+    for k in ("stride_Y", "stride_C", "plane_size_Y", "plane_size_C"):
+        h[k] = g[k]
+    return bytes(buf)
+
+
+def _rows(g):
+    return g["height_mbs"] * 16
+
+
+LAYOUT_BAD = [
+    ("psY_plus4", lambda g: dict(plane_size_Y=g["stride_Y"] * _rows(g) + 4)),   # every chroma row 4 bytes off the alignment of stride_C
+    ("psY_plus8", lambda g: dict(plane_size_Y=g["stride_Y"] * _rows(g) + 8)),
+    ("psY_plus1", lambda g: dict(plane_size_Y=g["stride_Y"] * _rows(g) + 1)),
+    ("psY_short", lambda g: dict(plane_size_Y=g["stride_Y"] * _rows(g) - 16)),
+    ("psC_short", lambda g: dict(plane_size_C=g["stride_C"] * _rows(g) // 2 - 8)),
+    ("stride_Y_plus8", lambda g: dict(stride_Y=g["stride_Y"] + 8, plane_size_Y=1 << 20)),
+    ("stride_C_plus4", lambda g: dict(stride_C=g["stride_C"] + 4, plane_size_C=1 << 20)),
+    ("stride_C_small", lambda g: dict(stride_C=g["width_mbs"] * 16 - 8)),
+    ("frame_2GiB", lambda g: dict(plane_size_C=(1 << 31) - g["plane_size_Y"])),  # plane_size_Y + plane_size_C = 2^31: the kernels' offsets are 32-bit
+    ("frame_8GiB", lambda g: dict(plane_size_Y=(1 << 32) - 16, plane_size_C=(1 << 32) - 8)),
+]
+LAYOUT_GOOD = [
+    *[(f"layout_{k}", lambda g, k=k: layouts.geometry(g["width_mbs"], g["height_mbs"], k)) for k in layouts.LAYOUTS],
+    ("psY_plus16", lambda g: dict(plane_size_Y=g["stride_Y"] * _rows(g) + 16)),
+    ("psC_plus1", lambda g: dict(plane_size_C=g["stride_C"] * _rows(g) // 2 + 1)),  # (nothing lies behind chroma: its size needs no alignment)
+    ("frame_below_2GiB", lambda g: dict(plane_size_C=(1 << 31) - 1 - g["plane_size_Y"])),
+]
+
+
+@pytest.mark.parametrize("form", ["version4", "wire"])
+@pytest.mark.parametrize("name,over", LAYOUT_BAD, ids=[c[0] for c in LAYOUT_BAD])
+def test_layout_refused(gop, name, over, form):
+    for raw in gop:
+        raw = backend.packet_compact(raw) if form == "wire" else raw
+        bad = _geom(raw, over)
+        assert bad != raw
+        assert backend.packet_check(bad) == errno.EINVAL, name
+        assert backend.last_error()
+
+
+@pytest.mark.parametrize("form", ["version4", "wire"])
+@pytest.mark.parametrize("name,over", LAYOUT_GOOD, ids=[c[0] for c in LAYOUT_GOOD])
+def test_layout_accepted(gop, name, over, form):
+    for raw in gop:
+        raw = backend.packet_compact(raw) if form == "wire" else raw
+        assert backend.packet_check(_geom(raw, over)) == 0, (name, backend.last_error())
+
+
+@pytest.mark.parametrize("form", ["version4", "wire"])
+def test_restride_keeps_every_other_byte(gop, form):
+    """tests/layouts.py restride: the four layout fields change, nothing else; a wire packet keeps its form"""
+    for raw in gop:
+        raw = backend.packet_compact(raw) if form == "wire" else raw
+        for k, lay in layouts.LAYOUTS.items():
+            out = layouts.restride(raw, *lay)
+            assert len(out) == len(raw) and out[4] == raw[4]
+            diff = np.nonzero(np.frombuffer(out, np.uint8) != np.frombuffer(raw, np.uint8))[0]
+            assert set(diff.tolist()) <= set(range(16, 32)), (k, diff)
+            assert layouts.hdr_of(out) == dict(layouts.hdr_of(raw), **layouts.geometry(*P.Packet(raw).hdr[["width_mbs", "height_mbs"]].item(), k))
