@@ -244,6 +244,53 @@ static inline size_t e264_expand_area_bytes(const void *wire)
 	return (size_t)32 * h->width_mbs * h->height_mbs + e264_expanded_motion_bytes(wire);
 }
 
+/* A compact entry (one list: 12 bytes, `both` lists: 20) as what it stands for: the version-4 record, whose motion record lies at mot_off of the motion section,
+ * and that motion record (rec; returns its 8 or 16 bytes). */
+static inline uint32_t e264_compact_entry_expand(const uint8_t *e, int both, uint32_t mot_off, E264Mb *out, uint8_t rec[16])
+{
+	E264MbCompact k;
+	memcpy(&k, e, 12);
+	memset(out, 0, 32);
+	out->kind = E264_MB_INTER; out->flags = (uint8_t)(k.flags & ~E264_MBCF_LIST1);
+	out->qp[0] = k.qp[0]; out->qp[1] = k.qp[1]; out->qp[2] = k.qp[2];
+	out->slice = k.slice; out->dbk_slice = k.dbk_slice;
+	const uint32_t d[2] = {mot_off, both ? E264_MOT_HDR_UNI01 : (k.flags & E264_MBCF_LIST1) ? E264_MOT_HDR_UNI1 : E264_MOT_HDR_UNI0};
+	memcpy(out->modes, d, 8);
+	rec[0] = k.ref_slot; rec[1] = k.ref_idx; rec[2] = rec[3] = 0;
+	memcpy(rec + 4, k.mv, 4);
+	if (both) memcpy(rec + 8, e + 12, 8);
+	return both ? 16 : 8;
+}
+
+/* The entries of a (structurally sound) version-5 packet one after the other, in raster order: the sequential form of e264_expand_mb's address arithmetic,
+ * running counts instead of popcounts. */
+typedef struct E264CompactCursor {
+	const uint32_t *cbits, *bbits; /* bitmap words of the current row */
+	const uint8_t *e;              /* the next entry */
+	uint32_t x, wm, wpr;
+	uint32_t nc, nb;               /* compact / two-list macroblocks before it: its motion record lies 8 * (nc + nb) bytes behind the first compact one's */
+} E264CompactCursor;
+static inline void e264_cursor_init(E264CompactCursor *c, const uint8_t *wire)
+{
+	const E264FrameHdr *h = (const E264FrameHdr *)wire;
+	c->x = c->nc = c->nb = 0;
+	c->wm = h->width_mbs; c->wpr = ((const E264CompactHdr *)(wire + h->mbs_off))->words_per_row;
+	c->cbits = (const uint32_t *)(wire + h->mbs_off + 16) + 3 * (size_t)h->height_mbs;
+	c->bbits = c->cbits + (size_t)h->height_mbs * c->wpr;
+	c->e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, h->height_mbs);
+}
+/* the next macroblock's entry (*entry) and its class: 0 full record (32 bytes), 1 one list (12), 2 both lists (20) */
+static inline int e264_cursor_next(E264CompactCursor *c, const uint8_t **entry)
+{
+	const uint32_t w = c->x >> 5, bit = c->x & 31;
+	const int cls = (int)(c->cbits[w] >> bit & 1u) + (int)(c->bbits[w] >> bit & 1u); /* (bbits is a subset of cbits) */
+	*entry = c->e;
+	c->e += cls == 0 ? 32 : cls == 1 ? 12 : 20;
+	c->nc += cls > 0; c->nb += cls > 1;
+	if (++c->x == c->wm) { c->x = 0; c->cbits += c->wpr; c->bbits += c->wpr; }
+	return cls;
+}
+
 /* the version-4 record of macroblock (x, y) of a version-5 packet and, for a compact one, its motion record (8 or 16 bytes, *rec_bytes; 0 for a full record).
  * synth_off: mot_off of the FIRST compact macroblock's motion record (they follow one another in macroblock order).  THE definition of the expansion: the
  * device kernel restates it. */
@@ -260,19 +307,7 @@ static inline void e264_expand_mb(const uint8_t *wire, uint32_t x, uint32_t y, u
 	const uint8_t *e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, hm) + row_off[y] + 32u * x - 20u * c + 8u * b;
 	*rec_bytes = 0;
 	if (!(cw >> (x & 31) & 1u)) { memcpy(out, e, 32); return; }
-	const int both = (int)(bw >> (x & 31) & 1u);
-	E264MbCompact k;
-	memcpy(&k, e, 12);
-	memset(out, 0, 32);
-	out->kind = E264_MB_INTER; out->flags = (uint8_t)(k.flags & ~E264_MBCF_LIST1);
-	out->qp[0] = k.qp[0]; out->qp[1] = k.qp[1]; out->qp[2] = k.qp[2];
-	out->slice = k.slice; out->dbk_slice = k.dbk_slice;
-	const uint32_t d[2] = {synth_off + 8u * (row_cbase[y] + c) + 8u * (row_bbase[y] + b), both ? E264_MOT_HDR_UNI01 : (k.flags & E264_MBCF_LIST1) ? E264_MOT_HDR_UNI1 : E264_MOT_HDR_UNI0};
-	memcpy(out->modes, d, 8);
-	rec[0] = k.ref_slot; rec[1] = k.ref_idx; rec[2] = rec[3] = 0;
-	memcpy(rec + 4, k.mv, 4);
-	*rec_bytes = 8;
-	if (both) { memcpy(rec + 8, e + 12, 8); *rec_bytes = 16; }
+	*rec_bytes = e264_compact_entry_expand(e, (int)(bw >> (x & 31) & 1u), synth_off + 8u * (row_cbase[y] + c) + 8u * (row_bbase[y] + b), out, rec);
 }
 
 /* version 5 (e264_check_compact has said 0) -> canonical version 4: [header][slices][E264Mb x n][motion: the wire's records, then the compact macroblocks'][payload].

@@ -34,6 +34,7 @@ def test_validated_packets_keep_the_kernels_in_bounds():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sanitize", "kernel_fuzz.py"), "--per-packet", "2", "--stride", "9", "--seed", "7"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+    assert "the sanitized validator and the library agreed" in p.stdout
     assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")
 
 
@@ -46,4 +47,5 @@ def test_padded_layouts_keep_the_kernels_in_bounds():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sanitize", "kernel_fuzz.py"), "--layouts", "--stride", "12"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+    assert "the sanitized validator and the library agreed" in p.stdout
     assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")

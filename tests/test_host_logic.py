@@ -2,6 +2,7 @@
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -29,6 +30,23 @@ def test_library_exports_every_header_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/edge264_hip.h but not exported"
     assert set(names) == set(backend.EXPORTED_SYMBOLS)
+    # ... and nothing else (kernel stubs, template instantiations): the export list of edge264_amd/csrc/exports.map
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        assert {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()} == set(names)
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="no g++")
+def test_packet_validation_is_host_only_code():
+    """The gate in front of the GPU (edge264_amd/csrc/e264_check.cpp) is plain C++17: it compiles with the host compiler, all warnings on, without
+    a HIP include path, and names neither the HIP runtime nor the kernels' header -- so that it can be built and run under a sanitizer
+    (tools/sanitize/kernel_fuzz.py)."""
+    csrc = os.path.join(ROOT, "edge264_amd", "csrc")
+    p = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I" + ROOT, os.path.join(csrc, "e264_check.cpp")],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    for f in ("e264_check.cpp", "e264_check.h"):
+        assert not re.search(r"hip_runtime|e264_kernels", open(os.path.join(csrc, f)).read()), f
 
 
 def test_launch_count_slots_match_header():

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """tools/sanitize/kernel_fuzz.py -- CHECKING TOOL: is the packet validation (e264hip_packet_check, the product's host-side gate in front of every
-kernel launch) tight enough for the kernels?  Command packets of real streams and of the synthetic generator are damaged at random (bytes of the
+kernel launch) tight enough for the kernels, and does it stay inside the packet itself?  The verdict on every packet comes from the validation
+unit (edge264_amd/csrc/e264_check.cpp, host code only) built HERE with AddressSanitizer, on a heap block of exactly the packet's length, and must
+agree with the product library's.  Command packets of real streams and of the synthetic generator are damaged at random (bytes of the
 header, the slice tables, the macroblock records, the motion records, the coefficient payload); whatever the validation still ACCEPTS is run
 through the kernels' own source compiled for the host (tests/emu, here built with AddressSanitizer) -- a packet in its wire form (version 5,
 include/edge264_compact.h) through e264_expand_kernel's source first -- on buffers of exactly the sizes the back end
@@ -28,13 +30,15 @@ def asan_runtime():
 
 
 def build():
-    for src, out in (("pred_emu.cpp", "libe264_pred_emu_asan.so"), ("intra_emu.cpp", "libe264_intra_emu_asan.so")):
+    CSRC = os.path.join(ROOT, "edge264_amd", "csrc")
+    for src, out in ((os.path.join(EMU, "pred_emu.cpp"), "libe264_pred_emu_asan.so"), (os.path.join(EMU, "intra_emu.cpp"), "libe264_intra_emu_asan.so"),
+                     (os.path.join(CSRC, "e264_check.cpp"), "libe264_check_asan.so")):
         o = os.path.join(HERE, out)
-        deps = [os.path.join(EMU, src)] + glob.glob(os.path.join(ROOT, "edge264_amd", "csrc", "*.h")) + [os.path.join(ROOT, "include", "edge264_cmd.h"), os.path.join(ROOT, "include", "edge264_compact.h")]
+        deps = [src] + glob.glob(os.path.join(ROOT, "edge264_amd", "csrc", "*.h")) + [os.path.join(ROOT, "include", "edge264_cmd.h"), os.path.join(ROOT, "include", "edge264_compact.h")]
         if os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in deps):
             continue
         subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", "-fsanitize=address", "-shared-libasan", "-fno-omit-frame-pointer", "-O1", "-g", "-std=c++17", "-fPIC", "-shared",
-                        "-fvisibility=hidden", "-I" + EMU, "-Wno-unused-function", os.path.join(EMU, src), "-o", o], check=True)
+                        "-fvisibility=hidden", "-I" + EMU, "-Wno-unused-function", src, "-o", o], check=True)
 
 
 def main():
@@ -62,6 +66,8 @@ def main():
     libc.free.argtypes = [C.c_void_p]
     pe = C.CDLL(os.path.join(HERE, "libe264_pred_emu_asan.so"))
     ie = C.CDLL(os.path.join(HERE, "libe264_intra_emu_asan.so"))
+    ck = C.CDLL(os.path.join(HERE, "libe264_check_asan.so"))
+    ck.e264hip_packet_check.argtypes = [C.c_void_p, C.c_size_t]
     VPP = C.POINTER(C.c_void_p)
     pe.e264emu_pred_frame2.argtypes = [C.c_void_p, VPP, C.c_void_p]
     pe.e264emu_dbkparam_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -95,6 +101,21 @@ def main():
         return dpb_cache[(need, n_mbs)]
     tally = dict(packets=len(packets), mutations=0, accepted=0, rejected=0, rejected_against_the_slots=0, changed_nothing=0)
     by_section = {}
+    agreed = [0]
+
+    def packet_check(buf):
+        """the sanitized validation unit's verdict on an exact-size heap copy of the packet (a read past its end is a heap-buffer-overflow);
+        the product library must say the same"""
+        n = len(buf)
+        mem = libc.malloc(n)
+        C.memmove(mem, bytes(buf), n)
+        r = ck.e264hip_packet_check(mem, n)
+        libc.free(mem)
+        lib = backend.packet_check(bytes(buf))
+        assert r == lib, f"sanitized validator says {r}, the library {lib}: {bytes(buf[:80]).hex()}"
+        agreed[0] += 1
+        return r
+    AGREED = "the sanitized validator and the library agreed on every mutation: {} verdicts compared, the undamaged packets' included"
 
     def run_kernels(buf, need0, n_mbs):
         """the kernels' source on an exact-size heap copy of the packet (a read past its end is a heap-buffer-overflow); a wire packet (version 5) first
@@ -129,13 +150,15 @@ def main():
             for name, lay in layouts.LAYOUTS.items():
                 for pkt in (layouts.restride(raw, *lay), layouts.restride(backend.packet_compact(raw), *lay)):
                     h = layouts.hdr_of(pkt)
+                    assert packet_check(pkt) == 0
                     run_kernels(bytearray(pkt), h["plane_size_Y"] + h["plane_size_C"], W * H)
                     n += 1
         print(f"kernel_fuzz --layouts: {len(packets)} packets x {len(layouts.LAYOUTS)} layouts x 2 forms = {n} runs")
+        print(AGREED.format(agreed[0]))
         print("no sanitizer report: every packet the validation accepted kept the kernels inside their buffers")
         return 0
     for raw in packets:
-        assert backend.packet_check(raw) == 0
+        assert packet_check(raw) == 0
         pk = P.Packet(raw)
         h = pk.hdr
         W, H = int(h["width_mbs"]), int(h["height_mbs"])
@@ -154,12 +177,12 @@ def main():
             if bytes(buf) == raw:
                 tally["changed_nothing"] += 1
                 continue
-            if backend.packet_check(bytes(buf)) != 0:
+            if packet_check(buf) != 0:
                 tally["rejected"] += 1
                 s["rejected"] += 1
                 continue
             hm = P.Packet(bytes(buf)).hdr
-            # what e264hip_submit_* holds even a vetted packet against (check_slots_of): the picture it declares fits the stream's slots
+            # what e264hip_submit_* holds even a vetted packet against (e264_check_slots): the picture it declares fits the stream's slots
             if int(hm["plane_size_Y"]) + int(hm["plane_size_C"]) > need0 or int(hm["width_mbs"]) * int(hm["height_mbs"]) > W * H:
                 tally["rejected_against_the_slots"] += 1
                 continue
@@ -182,7 +205,7 @@ def main():
             if bytes(buf) == wire:
                 tally["changed_nothing"] += 1
                 continue
-            if backend.packet_check(bytes(buf)) != 0:
+            if packet_check(buf) != 0:
                 tally["rejected"] += 1
                 s["rejected"] += 1
                 continue
@@ -194,6 +217,7 @@ def main():
             s["accepted"] += 1
             run_kernels(buf, need0, W * H)
     print("kernel_fuzz:", tally)
+    print(AGREED.format(agreed[0]))
     for k, v in by_section.items():
         print(f"  bytes damaged in {k:15s} accepted {v['accepted']:6d}  rejected {v['rejected']:6d}")
     print("no sanitizer report: every packet the validation accepted kept the kernels inside their buffers")
