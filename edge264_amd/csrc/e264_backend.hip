@@ -59,12 +59,12 @@ struct E264Device {
 	hipStream_t q[NQ];         // compute lanes
 	hipStream_t qup = nullptr; // upload queue
 	hipStream_t qc = nullptr;  // download queue
-	int waves;                 // waves per frame workgroup of the deblocking kernel (5 macroblock rows each): 2, 4, 7 or 8
-	int intra_waves;           // waves per frame workgroup of the intra kernel (1 macroblock row each)
+	int waves;                 // option "waves": the deblocking kernel's form, a row of e264_forms (e264_plan.h)
+	int intra_waves;           // option "intra_waves": waves per frame workgroup of the intra kernel (1 macroblock row each), a row of e264_forms
 	std::atomic<int> lane_streams[NQ] = {}; // live streams bound to each lane (open, bind_lane, close): the lanes in use are those with one
 	int n_cus;                 // compute units of the device
 	int split_planes;          // option "split_planes" (default 1): the split-off pictures' intra pass with luma and chroma on two workgroups (e264_intra_planes_kernel)
-	int split_intra;           // option "split_intra" (default 1): in a submission that mixes I pictures with others, their intra pass runs on q2 from the start (E264Fork.n_nopred)
+	int split_intra;           // option "split_intra" (default 1): in a submission that mixes I pictures with others, their intra pass runs on q2 from the start (E264Plan.n_split)
 	int side_queue;            // option "side_queue": parameter kernel on a second queue beside the macroblock-parallel kernel
 	int upload_queue;          // option "upload_queue" (default 1): the H2D copies of host batches go through qup
 	hipStream_t q2[NQ];        // one second queue per compute lane (+ its fork / join events): lanes must not share one (their split submissions would queue behind each other)
@@ -432,18 +432,13 @@ API int e264hip_set_option(E264Device *dev, const char *name, int value)
 		dev->upload_queue = value != 0;
 		return prev;
 	}
-	if (!strcmp(name, "intra_waves")) {
-		int prev = dev->intra_waves;
-		if (value == 4 || value == 8 || value == 16) dev->intra_waves = value;
-		return prev;
-	}
-	if (!strcmp(name, "waves")) {
-		int prev = dev->waves;
-		// 100 + n: n luma / chroma waves (e264_deblock2_kernel); 110, 112 exist only in builds with strips of four macroblocks (E264_DBK_GS = 2):
-		// elsewhere they are refused (-1, setting kept) instead of silently running as 108
-		const bool gs2 = strstr(e264_kernel_build_flags(), "E264_DBK_GS=2") != nullptr;
-		if ((value == 110 || value == 112) && !gs2) return -1;
-		if (value == 2 || value == 4 || value == 7 || value == 8 || value == 106 || value == 107 || value == 108 || value == 110 || value == 112) dev->waves = value; // anything else keeps the setting
+	const bool intra = !strcmp(name, "intra_waves");
+	if (intra || !strcmp(name, "waves")) {
+		int &option = intra ? dev->intra_waves : dev->waves;
+		const int prev = option;
+		const E264Form *f = e264_form(intra, value);
+		if (f && !f->exists) return -1; // a kernel this build does not have (waves 110, 112 without E264_DBK_GS = 2): refused, setting kept, instead of silently running as 108
+		if (f) option = value; // anything else keeps the setting
 		return prev;
 	}
 	return -1;
@@ -622,28 +617,17 @@ static int highest_lane_in_use(E264Device *dev)
 }
 
 // Launches the kernels over a job table that already lives in HBM, on compute lane `lane`.
-// n_nopred: the table's LAST n_nopred jobs hold no inter / PCM macroblock (0: unknown or none)
-static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int max_mbs, int max_tiles, int mode, uint64_t *serial_out = nullptr, int n_nopred = 0)
+// in: the submission's part of the planner's input (n .. expand); the device's part is filled here
+static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int max_mbs, int max_tiles, E264PlanIn in, uint64_t *serial_out = nullptr)
 {
 	std::lock_guard<std::mutex> g(dev->lock);
+	static const int alone_env = getenv("E264_PLANES_ALONE") ? atoi(getenv("E264_PLANES_ALONE")) : 0; // (for A/B)
+	in.split_planes = dev->split_planes; in.split_intra = dev->split_intra; in.side_queue = dev->side_queue; in.waves = dev->waves; in.intra_waves = dev->intra_waves;
+	in.n_cus = dev->n_cus; in.max_lane = highest_lane_in_use(dev); in.has_q2 = dev->q2[lane] != nullptr; in.planes_alone = alone_env;
+	E264Plan plan;
+	e264_plan(in, plan);
 	hipEvent_t *marks = nullptr;
-	// (not with more than two lanes in use: lanes and second queues then share the runtime's hardware queues -- four by default, GPU_MAX_HW_QUEUES -- and a lane's
-	// kernels wait behind another lane's 2.7-ms intra pass: 38.7 k against 52.0 k frames/s without the split, tools/stagger_probe.py, profiles/r06_ablations.txt item 16)
-	const int max_lane = highest_lane_in_use(dev);
-	const bool split = (dev->split_intra == 2 || (dev->split_intra && max_lane < 2)) && dev->q2[lane] && n_nopred > 0 && n_nopred < n;
-	// Two workgroups per picture (luma, chroma: e264_intra_planes_kernel) for the pictures whose intra pass stands alone -- while they are few: each takes a whole CU
-	// (125 KB of LDS) from the prediction kernel of the others, and with more than ~320 other pictures in the submission their kernels outlast a one-workgroup pass
-	// anyway (tools/stagger_probe.py: 256 pictures out of phase 72.4 -> 84.9 k frames/s; 512: 88.7 -> 86.9 k without this rule; profiles/r06_ablations.txt item 18)
-	const int cu_budget = dev->n_cus * 3 / 8;
-	int planes = 0;
-	if (dev->split_planes && split && 2 * n_nopred <= cu_budget && n - n_nopred <= 320) planes |= 1;
-	// ... a kernel that has the lane to itself (an all-intra batch's intra pass, every batch's deblocking) may take every CU: 64 streams 38.2 -> 42.8 k frames/s,
-	// 128 streams 61.6 -> 69.8 k (gpurun_out/pa1; E264_PLANES_ALONE overrides for A/B)
-	static const int alone_env = getenv("E264_PLANES_ALONE") ? atoi(getenv("E264_PLANES_ALONE")) : 0;
-	const int cu_alone = alone_env > 0 ? alone_env : dev->n_cus / (max_lane + 1); // (the lanes in use run beside each other: a lane's share)
-	if (dev->split_planes && (mode & E264_RUN_NO_PRED) && 2 * n <= cu_alone) planes |= 2;
-	if (dev->split_planes && 2 * n <= cu_alone) planes |= 4; // ... and the deblocking kernel's luma and chroma groups (one stream: a P picture 0.89 ms, of which that kernel is most)
-	E264Fork fork = {dev->side_queue || split || planes ? dev->q2[lane] : nullptr, dev->forked[lane], dev->joined[lane], nullptr, dev->side_queue, split ? n_nopred : 0, planes};
+	E264Fork fork = {dev->q2[lane], dev->forked[lane], dev->joined[lane], nullptr};
 	if (dev->ktiming) {
 		if (dev->kev_used == dev->kev.size()) {
 			E264Device::Marks m;
@@ -652,12 +636,11 @@ static int launch(E264Device *dev, int lane, const E264Job *d_jobs, int n, int m
 			dev->kev.push_back(m);
 		}
 		E264Device::Marks &m = dev->kev[dev->kev_used++];
-		m.side = !split && dev->side_queue && fork.aux != nullptr && (mode & 2); // (the parameter kernel's own marks; in a split submission it stays on the lane and the intra phase [2..3] holds the join)
+		m.side = plan.param_where != E264_PARAM_ON_LANE; // (the parameter kernel's own marks; in a split submission it stays on the lane and the intra phase [2..3] holds the join)
 		marks = m.e; fork.amarks = m.a;
 	}
-	uint64_t counts[E264_LC_COUNT] = {};
-	HIPCHK(e264_launch_frames(d_jobs, n, max_mbs, max_tiles, mode, dev->waves | dev->intra_waves << 8, dev->q[lane], marks, &fork, counts), EIO);
-	for (int i = 0; i < E264_LC_COUNT; i++) dev->launch_counts[i] += counts[i];
+	HIPCHK(e264_launch_frames(d_jobs, in.n, max_mbs, max_tiles, plan, dev->q[lane], marks, fork), EIO);
+	e264_plan_counts(plan, dev->launch_counts);
 	const uint64_t serial = next_serial(dev, lane);
 	if (serial_out) *serial_out = serial;
 	return 0;
@@ -707,13 +690,17 @@ static int check_once(E264Stream *const *streams, int i)
 	return 0;
 }
 // The job table's order is the launcher's to choose: pictures without prediction work (I pictures) LAST, so that a mixed batch can start their intra pass
-// beside the others' parameter and prediction kernels (E264Fork.n_nopred = back)
+// beside the others' parameter and prediction kernels (E264PlanIn.n_nopred = back)
 struct JobOrder { int n, front = 0, back = 0; int slot(bool pred_work) { return pred_work ? front++ : n - 1 - back++; } };
-// e264_launch_frames' mode: the caller's (E264_RUN_ALL bits) + what the launcher knows from the validation of every packet (E264_RUN_NO_PRED, E264_RUN_NO_L1:
-// none holds an inter or PCM macroblock / predicts from list 1) + whether a wire packet is still to be unfolded on the lane
-static int run_mode(int mode, bool pred_work, bool has_l1, bool expand = false)
+// the submission's part of the planner's input: n pictures, the last n_nopred of the table without prediction work, the caller's mode (E264_RUN_ALL bits) and
+// what the validation of every packet says (some holds an inter or PCM macroblock / predicts from list 1)
+static E264PlanIn submission(int n, int n_nopred, int mode, bool pred_work, bool has_l1)
 {
-	return (mode & E264_RUN_ALL) | (pred_work ? 0 : E264_RUN_NO_PRED) | (has_l1 ? 0 : E264_RUN_NO_L1) | (expand ? E264_RUN_EXPAND : 0);
+	E264PlanIn in = {};
+	in.n = n; in.n_nopred = n_nopred;
+	in.recon = (mode & E264_RUN_RECON) != 0; in.deblock = (mode & E264_RUN_DEBLOCK) != 0;
+	in.pred_work = pred_work; in.has_l1 = has_l1;
+	return in;
 }
 
 API int e264hip_frame_submit(E264Stream *s, const void *packet, size_t bytes)
@@ -741,7 +728,9 @@ API int e264hip_frame_submit(E264Stream *s, const void *packet, size_t bytes)
 	hipError_t e = hipMemcpyAsync(st->d, st->h, bytes, hipMemcpyHostToDevice, q);
 	if (e == hipSuccess) e = hipMemcpyAsync(st->d_job, job, sizeof(*job), hipMemcpyHostToDevice, q);
 	uint64_t serial = 0;
-	r = e == hipSuccess ? launch(s->dev, s->lane, st->d_job, 1, pi.n_mbs(), e264_pred_tiles(pi.width_mbs, pi.height_mbs), run_mode(E264_RUN_ALL, pi.pred_work, pi.has_l1, pi.area), &serial) : fail(EIO, "hipMemcpyAsync packet", e);
+	E264PlanIn in = submission(1, 0, E264_RUN_ALL, pi.pred_work, pi.has_l1);
+	in.expand = pi.area != 0; // a wire packet: unfolded on the lane, in front of the four
+	r = e == hipSuccess ? launch(s->dev, s->lane, st->d_job, pi.n_mbs(), e264_pred_tiles(pi.width_mbs, pi.height_mbs), in, &serial) : fail(EIO, "hipMemcpyAsync packet", e);
 	// whatever was queued reads the staging slot: it is busy until the lane has passed this point, error or not
 	hipEventRecord(st->done, q);
 	st->busy = true;
@@ -857,7 +846,7 @@ API int e264hip_batch_submit(E264Batch *b, int mode)
 	for (auto &w : b->writes)
 		if (w.first->lane != b->lane) return fail(EINVAL, "a stream of the batch was bound to another lane after batch_create");
 	uint64_t serial = 0;
-	int r = launch(b->dev, b->lane, b->d_jobs, b->n, b->max_mbs, b->max_tiles, run_mode(mode, b->pred_work, b->has_l1), &serial, b->n_nopred);
+	int r = launch(b->dev, b->lane, b->d_jobs, b->max_mbs, b->max_tiles, submission(b->n, b->n_nopred, mode, b->pred_work, b->has_l1), &serial);
 	if (!r) for (auto &w : b->writes) publish_serial(w.first, w.second, serial);
 	return r;
 }
@@ -979,7 +968,7 @@ static int submit_host_impl(E264Device *dev, E264Stream *const *streams, const v
 		if (e == hipSuccess) e = hipStreamWaitEvent(q, jr.up, 0);
 	}
 	uint64_t serial = 0;
-	r = e == hipSuccess ? launch(dev, lane, d_jobs, n, max_mbs, max_tiles, run_mode(mode, order.back != n, batch_l1), &serial, order.back) : fail(EIO, "packet upload", e);
+	r = e == hipSuccess ? launch(dev, lane, d_jobs, max_mbs, max_tiles, submission(n, order.back, mode, order.back != n, batch_l1), &serial) : fail(EIO, "packet upload", e);
 	if (r && up != q) hipStreamSynchronize(up); // copies already queued must not outlive the error return unguarded
 	// the job table and the staging slots are busy until the lane has passed this point -- also on an error above: whatever
 	// part of the batch was queued still reads them

@@ -14,8 +14,10 @@
 //                        prediction + residual (+ PCM), which depend on nothing inside the frame.
 //   e264_intra_kernel (e264_intra.h)     ONE WORKGROUP PER FRAME, ONE WAVE PER MACROBLOCK ROW: intra MBs only, row y
 //                        may reconstruct macroblock x once row y-1 has finished macroblock x+1.
-//   e264_deblock_kernel (e264_dbk.h)     one workgroup per frame, five macroblock rows per wave in lockstep, two lines
-//                        per lane: the raster dependency order of H.264 in-loop deblocking.
+//   e264_deblock2_kernel (e264_dbk.h)    one workgroup per frame, eight waves that take groups of 8 luma rows and of 16 chroma rows
+//                        from one list, two lines per lane: the raster dependency order of H.264 in-loop deblocking
+//                        (SURVEY.md 8a a16).  e264_deblock_kernel (option "waves" below 100) is the earlier form: five rows per wave, luma and chroma.
+// Which form of each a submission gets (wave counts, two workgroups per picture, the second queue) is decided on the host: e264_plan.h.
 // Progress counters live in LDS, so the hand-off between rows never leaves the CU: no
 // agent-scope fences, no cross-XCD traffic, no placement assumption.  Chip-level parallelism
 // comes from many independent streams (one frame of each per launch), the north-star workload
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void e264_intra_kernel(const E264Job *jobs
 	intra_kernel_body<NW>(S, jobs[blockIdx.x], (int)threadIdx.x, use_bitmap != 0);
 }
 // The same pass with a picture's LUMA and CHROMA on two workgroups (blockIdx.y): intra prediction and residual of the two never meet (a chroma block predicts from
-// chroma samples only), so an I picture whose intra pass stands alone on the critical path -- a submission that mixes it with P / B pictures (E264Fork.n_nopred), one
+// chroma samples only), so an I picture whose intra pass stands alone on the critical path -- a submission that mixes it with P / B pictures (E264Plan.n_split), one
 // stream by itself -- gets two CUs instead of one.  Sixteen waves each; no bitmap (pictures without prediction work).
 __global__ __launch_bounds__(1024) void e264_intra_planes_kernel(const E264Job *jobs)
 {
@@ -380,7 +382,7 @@ __global__ __launch_bounds__(NW * 64) void e264_deblock2_kernel(const E264Job *j
 
 // The same walk with a picture's luma groups on one workgroup and its chroma groups on another (blockIdx.y): the two chains never meet (separate samples, the same
 // read-only parameters), so a picture that has the device to itself -- one stream, a small batch -- gets two CUs for the kernel that is most of its latency
-// (one workgroup per picture: 0.9 ms of a P picture's 0.9).  The back end's call (E264Fork.planes bit 2: few pictures).
+// (one workgroup per picture: 0.9 ms of a P picture's 0.9).  The planner's call (E264Plan.dbk = E264_DBK_PLANES: few pictures).
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void e264_deblock2_planes_kernel(const E264Job *jobs)
 {
@@ -502,115 +504,93 @@ extern "C" hipError_t e264_launch_expand(const E264Job *jobs, int n_jobs, int ma
 	return hipGetLastError();
 }
 
-extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int max_mbs, int max_tiles, int mode, int waves, hipStream_t stream, hipEvent_t *marks,
-	const E264Fork *fork, uint64_t *counts)
+// ---------------------------------------------------------------------------------
+// The launcher: executes an E264Plan (e264_plan.h), decides nothing
+// ---------------------------------------------------------------------------------
+static_assert(E264_PLAN_GS2 == (E264_DBK_GS == 2), "e264_plan.h and e264_dbk.h disagree about E264_DBK_GS");
+
+// the kernel of a row of e264_forms
+typedef void (*E264IntraKernel)(const E264Job *, int);
+static E264IntraKernel intra_kernel(E264IntraForm form)
+{
+	switch (form) {
+	case E264_INTRA_4: return e264_intra_kernel<4>;
+	case E264_INTRA_16: return e264_intra_kernel<16>;
+	default: return e264_intra_kernel<8>;
+	}
+}
+typedef void (*E264DbkKernel)(const E264Job *);
+static E264DbkKernel dbk_kernel(E264DbkForm form)
+{
+	switch (form) {
+	case E264_DBK_PLANES: return e264_deblock2_planes_kernel<8>;
+#if E264_DBK_GS == 2
+	case E264_DBK2_12: return e264_deblock2_kernel<12>;
+	case E264_DBK2_10: return e264_deblock2_kernel<10>;
+#endif
+	case E264_DBK2_8: return e264_deblock2_kernel<8>;
+	case E264_DBK2_7: return e264_deblock2_kernel<7>;
+	case E264_DBK2_6: return e264_deblock2_kernel<6>;
+	case E264_DBK_2: return e264_deblock_kernel<2>;
+	case E264_DBK_4: return e264_deblock_kernel<4>;
+	case E264_DBK_8: return e264_deblock_kernel<8>;
+	default: return e264_deblock_kernel<7>;
+	}
+}
+
+// the intra pass of n jobs on queue q
+static void launch_intra(E264IntraForm form, const E264Job *jobs, int n, hipStream_t q, int use_bitmap)
+{
+	if (form == E264_INTRA_PLANES) hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n, 2), dim3(1024), 0, q, jobs);
+	else hipLaunchKernelGGL(intra_kernel(form), dim3(n), dim3(e264_form(true, form)->block), 0, q, jobs, use_bitmap);
+}
+// the parameter kernel on queue q
+static void launch_param(E264ParamForm form, const E264Job *jobs, int n, int max_mbs, hipStream_t q)
+{
+	const dim3 grid((max_mbs + DP_MBS - 1) / DP_MBS, n);
+	if (form == E264_PARAM_SMALL) hipLaunchKernelGGL(e264_dbkparam2_kernel<false>, grid, dim3(DP_NT), 0, q, jobs);
+	else hipLaunchKernelGGL(e264_dbkparam2_kernel<true>, grid, dim3(DP_NT), 0, q, jobs);
+}
+// One kernel on the second queue from this point of the lane on; the lane waits for fork.joined where it needs the result
+template <class Launch>
+static void launch_beside(const E264Fork &fork, hipStream_t stream, bool marks, Launch launch)
+{
+	hipEventRecord(fork.forked, stream);
+	hipStreamWaitEvent(fork.aux, fork.forked, 0);
+	if (marks) hipEventRecord(fork.amarks[0], fork.aux);
+	launch(fork.aux);
+	if (marks) hipEventRecord(fork.amarks[1], fork.aux);
+	hipEventRecord(fork.joined, fork.aux);
+}
+
+extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int max_mbs, int max_tiles, const E264Plan &plan, hipStream_t stream, hipEvent_t *marks,
+	const E264Fork &fork)
 {
 	if (n_jobs <= 0)
 		return hipSuccess;
-	auto count = [&](int slot, int n) { if (counts) counts[slot] += (uint64_t)n; };
 	// wire packets first (before the marks: they bracket the four kernels; the whole-run clocks contain this one)
-	if (mode & E264_RUN_EXPAND) {
+	if (plan.expand) {
 		const hipError_t e = e264_launch_expand(jobs, n_jobs, max_mbs, stream);
 		if (e != hipSuccess)
 			return e;
-		count(E264_LC_EXPAND, n_jobs);
 	}
 	// marks (optional): 5 events recorded before / between / after the four launches
 	if (marks) hipEventRecord(marks[0], stream);
-	const bool dbkp = (mode & 2) != 0;
-	const bool no_l1 = (mode & E264_RUN_NO_L1) != 0; // no packet of the batch predicts from list 1: the parameter kernel's small form (eight workgroups per CU)
-	const int intra_waves_ = waves >> 8 ? waves >> 8 : waves & 255;
-	// split_slot: where the split-off pictures are counted (any wave count) instead of under the kernel's own slot
-	auto launch_intra = [&](const E264Job *j, int n, hipStream_t q, int use_bitmap, int split_slot = -1) {
-		const int slot = use_bitmap ? E264_LC_INTRA4_BITMAP : E264_LC_INTRA4_NOBITMAP; // (then + 1: 8 waves, + 2: 16 waves)
-		switch (intra_waves_) {
-		case 4: hipLaunchKernelGGL(e264_intra_kernel<4>, dim3(n), dim3(256), 0, q, j, use_bitmap); break;
-		case 16: hipLaunchKernelGGL(e264_intra_kernel<16>, dim3(n), dim3(1024), 0, q, j, use_bitmap); break;
-		default: hipLaunchKernelGGL(e264_intra_kernel<8>, dim3(n), dim3(512), 0, q, j, use_bitmap); break;
-		}
-		count(split_slot >= 0 ? split_slot : slot + (intra_waves_ == 4 ? 0 : intra_waves_ == 16 ? 2 : 1), n);
-	};
-	// a submission that mixes pictures without prediction work (the table's last n_nopred jobs: I pictures) with others: their intra pass starts NOW on the
-	// second queue (E264Fork.n_nopred, e264_kernels.h); the rest of this function then sees the other jobs only, up to deblocking
-	const int n_split = (fork && fork->aux && (mode & 1) && !(mode & E264_RUN_NO_PRED) && fork->n_nopred > 0 && fork->n_nopred < n_jobs) ? fork->n_nopred : 0;
-	const int n_front = n_jobs - n_split;
-	if (n_split) {
-		hipEventRecord(fork->forked, stream);
-		hipStreamWaitEvent(fork->aux, fork->forked, 0);
-		if (marks) hipEventRecord(fork->amarks[0], fork->aux);
-		if ((fork->planes & 1) && intra_waves_ == 16) {
-			hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n_split, 2), dim3(1024), 0, fork->aux, jobs + n_front);
-			count(E264_LC_INTRA_PLANES_SPLIT, n_split);
-		} else {
-			launch_intra(jobs + n_front, n_split, fork->aux, 0, E264_LC_INTRA_SPLIT);
-		}
-		if (marks) hipEventRecord(fork->amarks[1], fork->aux);
-		hipEventRecord(fork->joined, fork->aux);
-	}
-	// fork->where (optional): the parameter kernel reads nothing but the packet and is needed only by the deblocking kernel, so it can run on the second queue beside
-	// the prediction kernel (1; rounds 1 - 4: no gain, that kernel fills every CU) or beside the intra kernel (2; round 6: no gain either, profiles/r06_ablations.txt item 1)
-	const bool side = dbkp && fork && fork->aux && fork->where && !n_split; // (not when the second queue is taken)
-	const int where = side ? (fork->where == 2 ? 2 : 1) : 0;
-	auto launch_side = [&]() {
-		hipEventRecord(fork->forked, stream);
-		hipStreamWaitEvent(fork->aux, fork->forked, 0);
-		if (marks) hipEventRecord(fork->amarks[0], fork->aux);
-		if (no_l1) hipLaunchKernelGGL(e264_dbkparam2_kernel<false>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, fork->aux, jobs);
-		else hipLaunchKernelGGL(e264_dbkparam2_kernel<true>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, fork->aux, jobs);
-		count(no_l1 ? E264_LC_DBKP_SMALL : E264_LC_DBKP_GENERAL, n_jobs);
-		count(where == 2 ? E264_LC_DBKP_SIDE2 : E264_LC_DBKP_SIDE1, n_jobs);
-		if (marks) hipEventRecord(fork->amarks[1], fork->aux);
-		hipEventRecord(fork->joined, fork->aux);
-	};
-	if (where == 1)
-		launch_side();
-	else if (dbkp && !side) {
-		if (no_l1) hipLaunchKernelGGL(e264_dbkparam2_kernel<false>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, stream, jobs);
-		else hipLaunchKernelGGL(e264_dbkparam2_kernel<true>, dim3((max_mbs + DP_MBS - 1) / DP_MBS, n_jobs), dim3(DP_NT), 0, stream, jobs);
-		count(no_l1 ? E264_LC_DBKP_SMALL : E264_LC_DBKP_GENERAL, n_jobs);
-	}
+	// the split-off pictures (the table's last n_split) start NOW on the second queue; up to deblocking the lane sees the other jobs only
+	if (plan.n_split)
+		launch_beside(fork, stream, marks, [&](hipStream_t q) { launch_intra(plan.split, jobs + n_jobs - plan.n_split, plan.n_split, q, 0); });
+	auto param_beside = [&]() { launch_beside(fork, stream, marks, [&](hipStream_t q) { launch_param(plan.param, jobs, n_jobs, max_mbs, q); }); };
+	if (plan.param_where == E264_PARAM_BESIDE_PRED) param_beside();
+	else if (plan.param && plan.param_where == E264_PARAM_ON_LANE) launch_param(plan.param, jobs, n_jobs, max_mbs, stream);
 	if (marks) hipEventRecord(marks[1], stream);
-	// an all-intra batch (every picture of an I launch: E264_RUN_NO_PRED) has nothing for the prediction kernel: 34 816 workgroups that load their records and
-	// leave cost 0.12 ms per launch of 256 pictures; the intra kernel then scans without the bitmap those workgroups would have written
-	const bool no_pred = (mode & E264_RUN_NO_PRED) != 0;
-	if ((mode & 1) && !no_pred) {
-		hipLaunchKernelGGL(e264_pred_kernel, dim3(max_tiles, n_front), dim3(PT_NT), 0, stream, jobs, mode);
-		count(E264_LC_PRED, n_front);
-	}
+	if (plan.n_pred) hipLaunchKernelGGL(e264_pred_kernel, dim3(max_tiles, plan.n_pred), dim3(PT_NT), 0, stream, jobs, plan.pred_mode);
 	if (marks) hipEventRecord(marks[2], stream);
-	if (where == 2)
-		launch_side();
-	waves &= 255;
-	if ((mode & 1) && no_pred && fork && (fork->planes & 2) && intra_waves_ == 16) // a FEW pictures, all without prediction work (one stream's I picture): two CUs each
-	{
-		hipLaunchKernelGGL(e264_intra_planes_kernel, dim3(n_jobs, 2), dim3(1024), 0, stream, jobs);
-		count(E264_LC_INTRA_PLANES_ALONE, n_jobs);
-	} else if (mode & 1)
-		launch_intra(jobs, n_front, stream, no_pred ? 0 : 1);
-	if (n_split) hipStreamWaitEvent(stream, fork->joined, 0);
-	if (side) hipStreamWaitEvent(stream, fork->joined, 0); // (before the mark: with the parameter kernel beside it, "intra" is the phase both share)
+	if (plan.param_where == E264_PARAM_BESIDE_INTRA) param_beside();
+	if (plan.intra) launch_intra(plan.intra, jobs, plan.n_intra, stream, plan.intra_bitmap);
+	if (plan.n_split || plan.param_where != E264_PARAM_ON_LANE) hipStreamWaitEvent(stream, fork.joined, 0); // (before the mark: with the parameter kernel beside it, "intra" is the phase both share)
 	if (marks) hipEventRecord(marks[3], stream);
-	if ((mode & 2) && waves == 108 && fork && (fork->planes & 4)) // few pictures: two workgroups each (luma groups, chroma groups)
-	{
-		hipLaunchKernelGGL(e264_deblock2_planes_kernel<8>, dim3(n_jobs, 2), dim3(512), 0, stream, jobs);
-		count(E264_LC_DBK_PLANES, n_jobs);
-	} else if (mode & 2) {
-		switch (waves) { // waves per picture (default 8, set by the back end); 100 + n: luma / chroma waves (e264_deblock2_kernel)
-#if E264_DBK_GS == 2 // strips of four macroblocks: 12.6 KB of LDS per wave, twelve waves (three per SIMD) fit the CU
-		case 112: hipLaunchKernelGGL(e264_deblock2_kernel<12>, dim3(n_jobs), dim3(768), 0, stream, jobs); count(E264_LC_DBK2_12, n_jobs); break;
-		case 110: hipLaunchKernelGGL(e264_deblock2_kernel<10>, dim3(n_jobs), dim3(640), 0, stream, jobs); count(E264_LC_DBK2_10, n_jobs); break;
-#else
-		case 112: case 110:
-#endif
-		case 108: hipLaunchKernelGGL(e264_deblock2_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); count(E264_LC_DBK2_8, n_jobs); break;
-		case 107: hipLaunchKernelGGL(e264_deblock2_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); count(E264_LC_DBK2_7, n_jobs); break;
-		case 106: hipLaunchKernelGGL(e264_deblock2_kernel<6>, dim3(n_jobs), dim3(384), 0, stream, jobs); count(E264_LC_DBK2_6, n_jobs); break;
-		case 2: hipLaunchKernelGGL(e264_deblock_kernel<2>, dim3(n_jobs), dim3(128), 0, stream, jobs); count(E264_LC_DBK_2, n_jobs); break;
-		case 4: hipLaunchKernelGGL(e264_deblock_kernel<4>, dim3(n_jobs), dim3(256), 0, stream, jobs); count(E264_LC_DBK_4, n_jobs); break;
-		case 8: hipLaunchKernelGGL(e264_deblock_kernel<8>, dim3(n_jobs), dim3(512), 0, stream, jobs); count(E264_LC_DBK_8, n_jobs); break;
-		default: hipLaunchKernelGGL(e264_deblock_kernel<7>, dim3(n_jobs), dim3(448), 0, stream, jobs); count(E264_LC_DBK_7, n_jobs); break;
-		}
-	}
+	const bool planes = plan.dbk == E264_DBK_PLANES; // two workgroups of eight waves per picture: luma groups, chroma groups
+	if (plan.dbk) hipLaunchKernelGGL(dbk_kernel(plan.dbk), dim3(n_jobs, planes ? 2 : 1), dim3(planes ? 512 : e264_form(false, plan.dbk)->block), 0, stream, jobs);
 	if (marks) hipEventRecord(marks[4], stream);
 	return hipGetLastError();
 }

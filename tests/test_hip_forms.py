@@ -1,12 +1,13 @@
 """Every kernel form the launcher can choose, against the oracle.
 
-The launcher (e264_backend.hip launch(), e264_kernels.hip e264_launch_frames) picks different kernels for the same picture depending on
+The planner (edge264_amd/csrc/e264_plan.cpp e264_plan, fed by e264_backend.hip launch(), executed by e264_kernels.hip e264_launch_frames) picks
+different kernels for the same picture depending on
 the size and make-up of the submission, the lanes in use and the device options: two workgroups per picture or one for deblocking and for
 an all-I batch's intra pass, the split-off intra pass of a mixed batch's I pictures, the parameter kernel's small form when no picture
 predicts from list 1, the parameter kernel on the second queue.  Here every picture is compared with Oracle.decode_frame on the whole
-slot, and every submission's e264hip_launch_counts must equal what the rules say it chose (expected_forms below: the rule table of the
-launcher, computed from the device's CU count and the lanes that have live streams), so a test that means one form cannot silently run
-another.  The rule boundaries themselves (128 / 129 pictures, 48 / 49 split-off I pictures, 320 / 321 others on a 256-CU device) are
+slot, and every submission's e264hip_launch_counts must equal what the rules say it chose (expected_forms below: the rule table, written
+out here independently of the planner and computed from the device's CU count and the lanes that have live streams;
+tests/test_host_logic.py holds the planner to it on the CPU), so a test that means one form cannot silently run another.  The rule boundaries themselves (128 / 129 pictures, 48 / 49 split-off I pictures, 320 / 321 others on a 256-CU device) are
 taken with pictures of a few macroblocks."""
 import contextlib
 import json
@@ -42,7 +43,7 @@ def packet_info(v4: bytes, sent: bytes, how: str):
 
 
 def expected_forms(infos, cfg, n_cus, max_lane=0, expand=0):
-    """Pictures per kernel form for one submission of len(infos) pictures (the rule table of launch() / e264_launch_frames)"""
+    """Pictures per kernel form for one submission of len(infos) pictures (the rule table of e264_plan, e264_plan.cpp)"""
     c = Counter()
     n = len(infos)
     n_nopred = sum(not pw for pw, _ in infos)

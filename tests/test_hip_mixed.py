@@ -1,5 +1,5 @@
 """Submissions that mix I pictures with P / B pictures (streams whose GOPs are not in phase): the launcher starts the intra pass of the pictures without
-prediction work on the second queue beside the others' parameter and prediction kernels (E264Fork.n_nopred, edge264_amd/csrc/e264_kernels.h).  Same pictures
+prediction work on the second queue beside the others' parameter and prediction kernels (E264Plan.n_split, edge264_amd/csrc/e264_plan.h).  Same pictures
 as with the option off, as one stream at a time, and as the oracle's."""
 import hashlib
 

@@ -49,6 +49,81 @@ def test_packet_validation_is_host_only_code():
         assert not re.search(r"hip_runtime|e264_kernels", open(os.path.join(csrc, f)).read()), f
 
 
+class _PlanIn(ctypes.Structure):  # E264PlanIn of edge264_amd/csrc/e264_plan.h
+    _fields_ = [(k, ctypes.c_int) for k in ("n", "n_nopred")] + [(k, ctypes.c_bool) for k in ("recon", "deblock", "pred_work", "has_l1", "expand")] + \
+        [(k, ctypes.c_int) for k in ("split_planes", "split_intra", "side_queue", "waves", "intra_waves", "n_cus", "max_lane")] + \
+        [("has_q2", ctypes.c_bool), ("planes_alone", ctypes.c_int)]
+
+
+class _Plan(ctypes.Structure):  # E264Plan
+    _fields_ = [("n", ctypes.c_int), ("expand", ctypes.c_bool)] + [(k, ctypes.c_int) for k in ("n_split", "split", "param", "param_where", "n_pred", "pred_mode", "intra")] + \
+        [("intra_bitmap", ctypes.c_bool), ("n_intra", ctypes.c_int), ("dbk", ctypes.c_int)]
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="no g++")
+def test_launch_plan_is_host_only_code_and_obeys_the_rule_table(tmp_path):
+    """The launch rules (edge264_amd/csrc/e264_plan.cpp) are plain C++17: built here with the host compiler alone, all warnings on, no HIP include path.
+    For reconstruction + deblocking the launch counters the plan implies (e264_plan_counts) equal expected_forms of tests/test_hip_forms.py -- the rule
+    table written out independently, which the GPU tests hold the device's counters to -- on every point of: 64 / 256 / 304 CUs x highest lane in use 0..3 x
+    every value of split_planes, split_intra, side_queue x every "waves" of a product build x intra_waves 4 / 8 / 16 x second queue or none (then
+    side_queue 0 and no split) x list-1 motion x wire packets to unfold x (n, n_nopred) at 1, 2, 3 and at each rule's boundary and one past it
+    (2 n <= n_cus / (lane + 1); 2 n_nopred <= n_cus * 3 / 8; 320 others), n_nopred in {0, 1, n - 1, n}.  Reconstruction alone launches nothing of
+    deblocking and deblocking alone nothing of reconstruction, and no plan splits a submission whose pictures are all of one kind."""
+    import itertools
+    from edge264_amd import backend
+    from tests.test_hip_forms import expected_forms
+    csrc = os.path.join(ROOT, "edge264_amd", "csrc")
+    so = str(tmp_path / "libe264_plan.so")
+    p = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", os.path.join(csrc, "e264_plan.cpp"), "-o", so],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and not p.stderr.strip(), p.stderr[-3000:]
+    for f in ("e264_plan.cpp", "e264_plan.h"):
+        assert not re.search(r'#\s*include\s*[<"][^>"\n]*(hip/|hip_runtime|e264_kernels)', open(os.path.join(csrc, f)).read()), f
+    lib = ctypes.CDLL(so)
+    names = backend.LAUNCH_COUNT_NAMES
+    pin, plan, counts = _PlanIn(), _Plan(), (ctypes.c_uint64 * len(names))()
+    rin, rplan, nbytes = ctypes.byref(pin), ctypes.byref(plan), ctypes.sizeof(counts)
+
+    for f in (lib.e264_plan, lib.e264_plan_counts):
+        f.argtypes, f.restype = [ctypes.c_void_p, ctypes.c_void_p], None
+
+    def slots():
+        """pictures per slot of the plan for `pin`"""
+        lib.e264_plan(rin, rplan)
+        ctypes.memset(counts, 0, nbytes)
+        lib.e264_plan_counts(rplan, counts)
+        return counts[:]
+
+    DBK = [i for i, k in enumerate(names) if k.startswith("dbk")]
+    RECON = [i for i, k in enumerate(names) if k == "pred" or k.startswith("intra")]
+    assert len(DBK) == 14 and len(RECON) == 10 and len(names) == 26  # (the other two: n_cus, expand)
+    points = 0
+    for pin.n_cus, pin.max_lane in itertools.product((64, 256, 304), range(4)):
+        a, b = pin.n_cus // (2 * (pin.max_lane + 1)), pin.n_cus * 3 // 16
+        shapes = {(n, k) for n in (1, 2, 3, a, a + 1) for k in (0, 1, n - 1, n) if 0 <= k <= n}
+        shapes |= {(b + 1, b), (b + 2, b + 1), (b + 100, b), (b + 101, b + 1), (321, 1), (322, 1), (b + 320, b)}
+        for (n, k), l1 in itertools.product(sorted(shapes), (False, True)):
+            infos = [(True, l1)] * (n - k) + [(False, l1)] * k
+            pin.n, pin.n_nopred, pin.pred_work, pin.has_l1 = n, k, k != n, l1
+            for sp, si, sq, w, iw, q2, xp in itertools.product((0, 1), (0, 1, 2), (0, 1, 2), (2, 4, 7, 8, 106, 107, 108), (4, 8, 16), (True, False), (False, True)):
+                if sq and not q2:
+                    continue  # (the option cannot be set on a device without second queues)
+                pin.split_planes, pin.split_intra, pin.side_queue, pin.waves, pin.intra_waves, pin.has_q2, pin.expand = sp, si, sq, w, iw, q2, xp
+                pin.recon = pin.deblock = True
+                cfg = dict(split_planes=sp, split_intra=si if q2 else 0, side_queue=sq, waves=w, intra_waves=iw)
+                got, want = {nm: c for nm, c in zip(names, slots()) if c}, expected_forms(infos, cfg, pin.n_cus, pin.max_lane, n if xp else 0)
+                assert got == want, (got, want, cfg, dict(n=n, n_nopred=k, l1=l1, n_cus=pin.n_cus, max_lane=pin.max_lane, q2=q2))
+                assert plan.n_split in (0, k) and not (plan.n_split and k in (0, n))
+                pin.deblock = False
+                c = slots()
+                assert not any(c[i] for i in DBK) and plan.n_split in (0, k) and not (plan.n_split and k in (0, n))
+                pin.recon, pin.deblock = False, True
+                c = slots()
+                assert not any(c[i] for i in RECON) and plan.n_split == 0
+                points += 1
+    assert points > 500000
+
+
 def test_launch_count_slots_match_header():
     """e264hip_launch_counts: the slot names of the binding are E264_LC_NAMES of the header, in the order of its E264_LC_* enum,
     and the stub back end answers with the same keys"""
