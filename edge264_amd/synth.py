@@ -16,6 +16,11 @@ scaling_range, level_ends, mv_ends, chroma_qp_offsets) reach the values a
 packet may carry but the default draws never do.  Left unset they draw nothing
 from the generator, so the default bytes stay what bench.py and the seeded
 tests were written against (tests/test_synth_defaults.py).
+
+The structure options (place, partitions, mv_classes, both_lists, coded_all)
+decide what a picture is made of instead of drawing it: which macroblocks are
+intra, how many partitions of which interpolation class a tile holds, how many
+blocks carry a residual.  They follow the same rule: unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -96,6 +101,17 @@ def modes_chroma(a: bool, b: bool, d: bool) -> list[int]:
     return out
 
 
+# (xFrac, yFrac) of the vectors of each interpolation class (edge264_amd/csrc/e264_pred.h pred_class)
+_CLASS_FRACS = (
+    ((0, 0),),
+    ((1, 0), (2, 0), (3, 0)),
+    ((0, 1), (0, 2), (0, 3)),
+    ((1, 1), (1, 3), (3, 1), (3, 3)),
+    ((2, 1), (2, 2), (2, 3)),
+    ((1, 2), (3, 2)),
+)
+
+
 def range_end_options(r: np.random.Generator) -> dict:
     """Range-end options (StreamSynth's weight_denoms ... chroma_qp_offsets) drawn from r, each present half the time: what the randomised
     checking tools (tools/oracle_sweep.py, tools/emu_sweep.py) add to their other draws."""
@@ -133,7 +149,8 @@ class StreamSynth:
                  stress: bool = False, qp_base: int = 28, i_kinds=(P.MB_I4x4, P.MB_I16x16),
                  filter_offsets=(0, 0), deblock_idc: int = 0, n_slots: int = 6,
                  weight_denoms=None, weight_range=(-32, 96), offset_range=(-20, 20), weight_pins: float = 0.0,
-                 scaling_range=(8, 40), level_ends: bool = False, mv_ends: float = 0.0, chroma_qp_offsets=None):
+                 scaling_range=(8, 40), level_ends: bool = False, mv_ends: float = 0.0, chroma_qp_offsets=None,
+                 place=None, partitions=None, mv_classes=None, both_lists: bool = False, coded_all: bool = False):
         """The range-end options:
         weight_denoms      (luma, chroma) log2 weight denominator pairs, one drawn per explicitly weighted slice (default: each of 3..6)
         weight_range       explicit weights drawn from [lo, hi]; offset_range: explicit offsets from [lo, hi]
@@ -143,7 +160,18 @@ class StreamSynth:
         level_ends         per macroblock, one of: the usual levels; int16 ends (+-32767, -32768, +-16000, 127, -128, 128, -129) in
                            every block including the DC ones; byte-form ends (every AC level in -128..127, -128 and 127 both present)
         mv_ends            probability that a vector component is pinned near an int16 end (+-32768 quarter samples)
-        chroma_qp_offsets  (Cb, Cr) chroma QP offsets instead of two drawn from -3..3"""
+        chroma_qp_offsets  (Cb, Cr) chroma QP offsets instead of two drawn from -3..3
+        The structure options:
+        place              function (mbx, mby, W, H) -> None | "intra" | "inter" | "pcm", asked for every macroblock of a P or B picture;
+                           None: drawn as without it
+        partitions         "4x4": every inter macroblock is four 8x8 quadrants of four 4x4 partitions whose four vectors differ pairwise
+                           (per list), never with the 8x8 transform
+        mv_classes         tuple out of 0..5: the fractional part of every vector is drawn so that the vector's interpolation class (0 integer,
+                           1 yFrac 0, 2 xFrac 0, 3 both odd, 4 xFrac 2 and yFrac != 0, 5 yFrac 2 and xFrac odd) is one of them; the integer
+                           part stays within the range the vector is drawn from (mv_range); mv_ends does not apply
+        both_lists         every quadrant of a B macroblock predicts from both lists
+        coded_all          every inter macroblock carries chroma DC and all 16 + 8 4x4 blocks; with t8x8 (and not partitions="4x4") all of
+                           them have the 8x8 transform and carry its four blocks"""
         self.w, self.h = width_mbs, height_mbs
         self.rng = np.random.default_rng(seed)
         self.t8x8, self.scaling, self.weighted, self.deblock = t8x8, scaling, weighted, deblock
@@ -160,6 +188,9 @@ class StreamSynth:
         self.weight_range, self.offset_range, self.weight_pins = tuple(weight_range), tuple(offset_range), weight_pins
         self.scaling_range, self.level_ends, self.mv_ends = tuple(scaling_range), level_ends, mv_ends
         self.lev_mode = 0  # level_ends: 0 usual, 1 int16 ends, 2 byte-form ends (drawn per macroblock)
+        assert partitions in (None, "4x4") and all(0 <= c <= 5 for c in (mv_classes or ()))
+        self.place, self.partitions, self.both_lists, self.coded_all = place, partitions, both_lists, coded_all
+        self.mv_classes = tuple(mv_classes) if mv_classes else None
         if chroma_qp_offsets is not None:
             self.cqp_off = (int(chroma_qp_offsets[0]), int(chroma_qp_offsets[1]))
         else:
@@ -302,18 +333,28 @@ class StreamSynth:
             qps = (qp, chroma_qp(qp, self.cqp_off[0]), chroma_qp(qp, self.cqp_off[1]))
             if self.level_ends:
                 self.lev_mode = int(rng.integers(0, 3))
-            inter = ftype != "I" and rng.random() >= self.intra_in_inter
-            if not inter and rng.random() < self.pcm_prob:
+            placed = self.place(mbx, mby, W, H) if self.place is not None and ftype != "I" else None
+            if placed is None:
+                inter = ftype != "I" and rng.random() >= self.intra_in_inter
+                pcm = not inter and rng.random() < self.pcm_prob
+            else:
+                assert placed in ("intra", "inter", "pcm"), placed
+                inter, pcm = placed == "inter", placed == "pcm"
+            if pcm:
                 b.set_mb(addr, kind=P.MB_PCM, slice_idx=sidx, qp=(0, chroma_qp(0, self.cqp_off[0]), chroma_qp(0, self.cqp_off[1])),
                          flags=flags, nz_mask=0xffff, pcm=rng.integers(0, 256, 384, dtype=np.uint8).tobytes())
                 continue
             luma_blocks, chroma_blocks, luma_dc, chroma_dc = {}, {}, None, None
-            has_res = (not inter) or rng.random() < self.residual_prob
+            full = inter and self.coded_all
+            has_res = (not inter) or full or rng.random() < self.residual_prob
             kind = P.MB_INTER
             t8 = False
             kw = {}
             if inter:
-                t8 = self.t8x8 and rng.random() < 0.5
+                if self.partitions == "4x4":
+                    t8 = False
+                else:
+                    t8 = self.t8x8 and (full or rng.random() < 0.5)
                 kw["motion"] = self._motion(ftype, l0, l1, t8)
             else:
                 kinds = list(self.i_kinds)
@@ -361,12 +402,12 @@ class StreamSynth:
                                 nz |= 1 << k
                 elif t8:
                     for blk in range(4):
-                        if rng.random() < 0.6:
+                        if full or rng.random() < 0.6:
                             luma_blocks[blk * 4] = self._levels(64, qp, 8, 4)
                             nz |= 0xf << (blk * 4)
                 else:
                     for k in range(16):
-                        if rng.random() < 0.5:
+                        if full or rng.random() < 0.5:
                             luma_blocks[k] = self._levels(16, qp, 6, 3)
                             nz |= 1 << k
                 if self.lev_mode == 2 and not luma_blocks:  # byte-form ends need an AC block
@@ -374,12 +415,12 @@ class StreamSynth:
                     c[0] = 0 if kind == P.MB_I16x16 else c[0]
                     luma_blocks[0] = c if not t8 else np.resize(c, 64)
                     nz |= 1 if not t8 else 0xf
-                if rng.random() < 0.6:
+                if full or rng.random() < 0.6:
                     chroma_dc = self._levels(16, qps[1], 4, 4)[:8].copy()
                     chroma_dc[0] |= 1
-                    if rng.random() < 0.5:
+                    if full or rng.random() < 0.5:
                         for k in range(8):
-                            if rng.random() < 0.5:
+                            if full or rng.random() < 0.5:
                                 c = self._levels(16, qps[1 + (k >> 2)], 4, 3)
                                 c[0] = 0
                                 chroma_blocks[k] = c
@@ -405,10 +446,15 @@ class StreamSynth:
             shape = 1  # 16x8 / 8x16
         else:
             shape = 2  # 8x8 with sub-partitions
+        if self.partitions == "4x4":
+            shape = 2
         big = rng.random() < 0.05
         rangemv = self.mv_range * (16 if big else 1)
 
         def mv():
+            if self.mv_classes:
+                fracs = _CLASS_FRACS[self.mv_classes[int(rng.integers(0, len(self.mv_classes)))]]
+                return rng.integers(-(rangemv // 4), max(rangemv // 4, 1), 2) * 4 + fracs[int(rng.integers(0, len(fracs)))]
             v = rng.integers(-rangemv, rangemv + 1, 2)
             if self.mv_ends:
                 for j in range(2):
@@ -417,6 +463,8 @@ class StreamSynth:
             return v
         if ftype == "P":
             use = [(True, False)] * 4
+        elif self.both_lists:
+            use = [(True, True)] * 4
         else:
             opts = [(True, False), (False, True), (True, True)]
             if shape == 0:
@@ -459,6 +507,10 @@ class StreamSynth:
                         continue
                     sub = int(rng.integers(0, 4)) if not t8 else 0  # 8x8, 8x4, 4x8, 4x4
                     v = [mv() for _ in range(4)]
+                    if self.partitions == "4x4":
+                        sub = 3
+                        while len({(int(a[0]), int(a[1])) for a in v}) < 4:
+                            v = [mv() for _ in range(4)]
                     for j in range(4):
                         sel = [0, j >> 1, j & 1, j][sub]
                         mvs[lx, b8 * 4 + j] = v[sel]

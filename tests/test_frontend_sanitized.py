@@ -49,3 +49,16 @@ def test_padded_layouts_keep_the_kernels_in_bounds():
     assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
     assert "the sanitized validator and the library agreed" in p.stdout
     assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang++") or not os.path.exists(os.path.join(ROOT, "edge264_amd", "libedge264_hip.so")),
+                    reason="needs the ROCm clang (ASan runtime) and the built back end (its host-side packet validation)")
+def test_saturated_lists_keep_the_kernels_in_bounds():
+    """tools/sanitize/kernel_fuzz.py --structure: the pictures of tests/structure_cases.py that fill a class list of the prediction kernel to its
+    last slot, or a tile's residual lists, through the kernels' source under AddressSanitizer on exact-size buffers, both packet forms: an item
+    read from beyond a list would send its lane to a macroblock outside the tile."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sanitize", "kernel_fuzz.py"), "--structure"],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "no sanitizer report" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+    assert "the sanitized validator and the library agreed" in p.stdout
+    assert "AddressSanitizer" not in p.stderr.replace("ASan doesn't fully support", "")

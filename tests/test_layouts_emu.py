@@ -114,13 +114,14 @@ def check_slots(hdr, before, after, label):
             raise AssertionError(L.first_difference(hdr, a, want, f"{label}: slot {s}" + (" (destination, outside its samples)" if s == d else " (not the destination)")))
 
 
-def run_case(libs, variant, layout, w, h, pattern, kw, seed, absent=False, oracle=None, name=""):
-    g = synth.StreamSynth(w, h, seed, **kw)
+def run_case(libs, variant, layout, w, h, pattern, kw, seed, absent=False, oracle=None, name="", packets=None):
+    """packets: the stream's tight packets, where the caller has generated them already (pattern, kw and seed then only label the run)"""
+    g = synth.StreamSynth(w, h, seed, **kw) if packets is None else None
     rng = np.random.default_rng(seed + 17)
     oracle = oracle or Oracle()
     mine = theirs = None
     for i, t in enumerate(pattern):
-        raw = bytes(g.next_frame(t))
+        raw = bytes(g.next_frame(t) if packets is None else packets[i])
         if absent and i:
             raw = lose_macroblocks(raw, rng)
         v4 = L.in_layout(raw, layout)

@@ -10,7 +10,7 @@ import pytest
 
 from edge264_amd import packet as P
 from edge264_amd import synth
-from tests import edge_cases, layouts
+from tests import edge_cases, layouts, structure_cases
 
 W, H = 6, 5
 ALL_I = (P.MB_I8x8, P.MB_I4x4, P.MB_I16x16)
@@ -142,6 +142,18 @@ def test_range_ends_wide(oracle, refkernels):
     run_stream(oracle, refkernels, 9, "IPBP", dict(mv_ends=0.3, weighted=1, weight_denoms=[(7, 7)], weight_pins=0.3, t8x8=True,
                                                     i_kinds=ALL_I), 120, 3, seen=seen)
     assert seen["mv_ends"] and seen["denom7_default"] and seen["bipred_and128"], seen
+
+
+STRUCTURE = [(c[0], w, h) for c in structure_cases.SATURATED for (w, h) in c[1]]
+
+
+@pytest.mark.parametrize("name,w,h", STRUCTURE, ids=[f"{n}_{w}x{h}" for n, w, h in STRUCTURE])
+def test_saturated_structure(oracle, refkernels, name, w, h):
+    """The pictures of tests/structure_cases.py that fill a tile's class lists and residual lists (1024 4x4 partitions of one interpolation
+    class, every block of every macroblock coded): the oracle stays pinned to the reference's kernels where the kernel tests lean on it."""
+    _, _, pattern, kw, _ = structure_cases.CASES[name]
+    structure_cases.check(name, w, h)  # (the packets run_stream makes from the same seed and options: their census)
+    run_stream(oracle, refkernels, structure_cases.seed_of(name, w, h), pattern, kw, w, h)
 
 
 LAYOUT_CASES = [c for c in CASES if c[0] in ("intra8x8", "pcm", "ibbp_explicit_wp", "ibbp_implicit_wp", "slices_idc2", "stress_implicit_far_mv")]

@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--stride", type=int, default=1, help="take every K-th packet of the corpus (the quick form used by tests/test_frontend_sanitized.py)")
     ap.add_argument("--layouts", action="store_true", help="no damage: every packet in every padded layout of tests/layouts.py, both packet forms")
+    ap.add_argument("--structure", action="store_true", help="no damage: the saturated-list and full-residual pictures of tests/structure_cases.py, both packet forms")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if not args.child:
@@ -56,7 +57,7 @@ def main():
             return 2
         build()
         env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0:allocator_may_return_null=1")
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--per-packet", str(args.per_packet), "--seed", str(args.seed), "--stride", str(args.stride)] + (["--layouts"] if args.layouts else []), env=env)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--per-packet", str(args.per_packet), "--seed", str(args.seed), "--stride", str(args.stride)] + (["--layouts"] if args.layouts else []) + (["--structure"] if args.structure else []), env=env)
         return p.returncode
     import numpy as np
     from edge264_amd import backend, front, packet as P, synth
@@ -87,6 +88,9 @@ def main():
         except TypeError:
             packets += [bytes(p) for p in synth.StreamSynth(5, 4, seed=seed, num_refs=2).gop("IPBPB")]
     packets = packets[::max(1, args.stride)]
+    if args.structure:  # class lists filled to the last slot, the residual lists as full as a tile makes them: the most any list index reaches
+        from tests import structure_cases
+        packets = [p for c in structure_cases.SATURATED for (w, h) in c[1] for p in structure_cases.check(c[0], w, h)[1:]]  # (the P and the B picture)
     rng = np.random.default_rng(args.seed)
     dpb_cache = {}
 
@@ -142,18 +146,19 @@ def main():
         if area:
             libc.free(area)
 
-    if args.layouts:
+    if args.layouts or args.structure:
         from tests import layouts
         n = 0
+        lays = layouts.LAYOUTS if args.layouts else {k: layouts.LAYOUTS[k] for k in ("tight", "pad16")}
         for raw in packets:
             W, H = int(P.Packet(raw).hdr["width_mbs"]), int(P.Packet(raw).hdr["height_mbs"])
-            for name, lay in layouts.LAYOUTS.items():
+            for name, lay in lays.items():
                 for pkt in (layouts.restride(raw, *lay), layouts.restride(backend.packet_compact(raw), *lay)):
                     h = layouts.hdr_of(pkt)
                     assert packet_check(pkt) == 0
                     run_kernels(bytearray(pkt), h["plane_size_Y"] + h["plane_size_C"], W * H)
                     n += 1
-        print(f"kernel_fuzz --layouts: {len(packets)} packets x {len(layouts.LAYOUTS)} layouts x 2 forms = {n} runs")
+        print(f"kernel_fuzz {'--layouts' if args.layouts else '--structure'}: {len(packets)} packets x {len(lays)} layouts x 2 forms = {n} runs")
         print(AGREED.format(agreed[0]))
         print("no sanitizer report: every packet the validation accepted kept the kernels inside their buffers")
         return 0
