@@ -160,55 +160,63 @@ template <int K> E264_DEV DkRole dk_role(int lane)
 template <int STRONG, bool LUMA>
 E264_DEV void dk_edge(s16x2 *v, s16x2 alphaE, s16x2 beta, s16x2 betal, s16x2 tc0, s16x2 small_thr, s16x2 strong)
 {
-	s16x2 &p3 = v[0], &p2 = v[1], &p1 = v[2], &p0 = v[3], &q0 = v[4], &q1 = v[5], &q2 = v[6], &q3 = v[7];
+	// The eight values are read before the first branch and the (up to) six results written after the last join: between the two nothing
+	// refers to v[], so what meets at a join are the results' own registers and never the caller's array (round 7, DESIGN.md section 4.2: written
+	// inside the branches, the chroma walk's array crossed every join as one <40 x i16> value and was rebuilt behind it register by register).
+	const s16x2 p3 = v[0], p2 = v[1], p1 = v[2], p0 = v[3], q0 = v[4], q1 = v[5], q2 = v[6], q3 = v[7];
+	s16x2 np2 = p2, np1 = p1, np0 = p0, nq0 = q0, nq1 = q1, nq2 = q2;
+	do {
 #if E264_DBK_ALSKIP // (wave-uniform) no lane has a boundary strength here: not even the three differences are needed (encoder-made content: 89 % of all bS are 0)
-	if (!DK_ANY(as_u(alphaE)))
-		return;
+		if (!DK_ANY(as_u(alphaE)))
+			break;
 #endif
-	const s16x2 d = p0 - q0, dpq = dk_abs(d);
-	// filterSamplesFlag: all three differences below their thresholds <=> all three (difference - threshold) negative
-	const s16x2 go = ((dpq - alphaE) & (dk_abs(p1 - p0) - beta) & (dk_abs(q1 - q0) - beta)) >> 15;
+		const s16x2 d = p0 - q0, dpq = dk_abs(d);
+		// filterSamplesFlag: all three differences below their thresholds <=> all three (difference - threshold) negative
+		const s16x2 go = ((dpq - alphaE) & (dk_abs(p1 - p0) - beta) & (dk_abs(q1 - q0) - beta)) >> 15;
 #ifdef E264_ABL_DBK_NOFILTER // timing ablation
-	if (as_u(go) != 0x12345) return;
+		if (as_u(go) != 0x12345) break;
 #endif
 #ifndef E264_DBK_NOEARLY // (measuring aid: what the wave-wide "no lane filters this edge" test is worth)
-	if (!DK_ANY(as_u(go)))
-		return;
+		if (!DK_ANY(as_u(go)))
+			break;
 #endif
-	const s16x2 zero2 = {0, 0};
-	const s16x2 ap = LUMA ? ((dk_abs(p2 - p0) - betal) >> 15) & go : zero2, aq = LUMA ? ((dk_abs(q2 - q0) - betal) >> 15) & go : zero2;
-	// ---- bS < 4
-	const s16x2 tc = tc0 - ap - aq;
-	const s16x2 delta = dk_clip((d * (short)-4 + p1 - q1 + (short)4) >> 3, -tc, tc) & go;
-	const s16x2 avg = as_s2(v_lerp_u8(as_u(p0), as_u(q0), 0x00010001u)); // (p0 + q0 + 1) >> 1
-	const s16x2 z = {0, 0}, m255 = {255, 255};
-	const s16x2 dp1 = LUMA ? dk_clip((p2 + avg - p1 * (short)2) >> 1, -tc0, tc0) & ap : zero2; // tc0 is 0 on bS 4 lines: p1 stays
-	const s16x2 dq1 = LUMA ? dk_clip((q2 + avg - q1 * (short)2) >> 1, -tc0, tc0) & aq : zero2;
+		const s16x2 zero2 = {0, 0};
+		const s16x2 ap = LUMA ? ((dk_abs(p2 - p0) - betal) >> 15) & go : zero2, aq = LUMA ? ((dk_abs(q2 - q0) - betal) >> 15) & go : zero2;
+		// ---- bS < 4
+		const s16x2 tc = tc0 - ap - aq;
+		const s16x2 delta = dk_clip((d * (short)-4 + p1 - q1 + (short)4) >> 3, -tc, tc) & go;
+		const s16x2 avg = as_s2(v_lerp_u8(as_u(p0), as_u(q0), 0x00010001u)); // (p0 + q0 + 1) >> 1
+		const s16x2 z = {0, 0}, m255 = {255, 255};
+		const s16x2 dp1 = LUMA ? dk_clip((p2 + avg - p1 * (short)2) >> 1, -tc0, tc0) & ap : zero2; // tc0 is 0 on bS 4 lines: p1 stays
+		const s16x2 dq1 = LUMA ? dk_clip((q2 + avg - q1 * (short)2) >> 1, -tc0, tc0) & aq : zero2;
 #if E264_DBK_SATPACK // p0 / q0 leave the edge unclipped (-27 .. 282): the pack back to bytes saturates them (dk_vpass / dk_hpass), 4 instructions per edge fewer
-	s16x2 np0 = p0 + delta, nq0 = q0 - delta;
+		np0 = p0 + delta; nq0 = q0 - delta;
 #else
-	s16x2 np0 = dk_clip(p0 + delta, z, m255), nq0 = dk_clip(q0 - delta, z, m255);
+		np0 = dk_clip(p0 + delta, z, m255); nq0 = dk_clip(q0 - delta, z, m255);
 #endif
-	s16x2 np1 = p1 + dp1, nq1 = q1 + dq1;
-	if (STRONG) {
-		const s16x2 S = strong & go;
-		if (DK_ANY(as_u(S))) { // ---- bS == 4
-			const s16x2 wp0 = (p1 * (short)2 + p0 + q1 + (short)2) >> 2, wq0 = (q1 * (short)2 + q0 + p1 + (short)2) >> 2;
-			np0 = dk_sel(S, wp0, np0); nq0 = dk_sel(S, wq0, nq0);
-			if (STRONG == 1) {
-				const s16x2 sm = (dpq - small_thr) >> 15; // |p0 - q0| < (alpha >> 2) + 2
-				const s16x2 sp = ap & sm & S, sq = aq & sm & S;
-				const s16x2 pq = p0 + q0, tp = p2 + p1 + pq, tq = q2 + q1 + pq;
-				np0 = dk_sel(sp, (tp + p1 + pq + q1 + (short)4) >> 3, np0);
-				nq0 = dk_sel(sq, (tq + q1 + pq + p1 + (short)4) >> 3, nq0);
-				np1 = dk_sel(sp, (tp + (short)2) >> 2, np1);
-				nq1 = dk_sel(sq, (tq + (short)2) >> 2, nq1);
-				p2 = dk_sel(sp, ((p3 + p2) * (short)2 + tp + (short)4) >> 3, p2);
-				q2 = dk_sel(sq, ((q3 + q2) * (short)2 + tq + (short)4) >> 3, q2);
+		np1 = p1 + dp1; nq1 = q1 + dq1;
+		if (STRONG) {
+			const s16x2 S = strong & go;
+			if (DK_ANY(as_u(S))) { // ---- bS == 4
+				const s16x2 wp0 = (p1 * (short)2 + p0 + q1 + (short)2) >> 2, wq0 = (q1 * (short)2 + q0 + p1 + (short)2) >> 2;
+				np0 = dk_sel(S, wp0, np0); nq0 = dk_sel(S, wq0, nq0);
+				if (STRONG == 1) {
+					const s16x2 sm = (dpq - small_thr) >> 15; // |p0 - q0| < (alpha >> 2) + 2
+					const s16x2 sp = ap & sm & S, sq = aq & sm & S;
+					const s16x2 pq = p0 + q0, tp = p2 + p1 + pq, tq = q2 + q1 + pq;
+					np0 = dk_sel(sp, (tp + p1 + pq + q1 + (short)4) >> 3, np0);
+					nq0 = dk_sel(sq, (tq + q1 + pq + p1 + (short)4) >> 3, nq0);
+					np1 = dk_sel(sp, (tp + (short)2) >> 2, np1);
+					nq1 = dk_sel(sq, (tq + (short)2) >> 2, nq1);
+					np2 = dk_sel(sp, ((p3 + p2) * (short)2 + tp + (short)4) >> 3, p2);
+					nq2 = dk_sel(sq, ((q3 + q2) * (short)2 + tq + (short)4) >> 3, q2);
+				}
 			}
 		}
-	}
-	p0 = np0; q0 = nq0; p1 = np1; q1 = nq1;
+	} while (0);
+	if (STRONG == 1) { v[1] = np2; v[6] = nq2; }
+	if (LUMA) { v[2] = np1; v[5] = nq1; }
+	v[3] = np0; v[4] = nq0;
 }
 
 // The parameters of the four edge slots of a lane for one direction, ready for dk_edge.  They are fetched for BOTH
