@@ -27,7 +27,8 @@
 // macroblocks of its last row have left for memory (progress[]), the wave below fetches the top rows of a group of 4 once
 // that group is there.  Nothing else synchronises: the five rows of a wave run in lockstep by construction.
 //
-// Every function here is a plain function of (LDS, frame, lane role, step): tests/emu runs them on the host.
+// The per-lane helpers are plain functions of (LDS, frame, lane role, step); the walk and the three kernels' bodies at the end
+// are written against the collectives of e264_dev.h: tests/emu runs them on the host as they are.
 #ifndef E264_DBK_H
 #define E264_DBK_H
 #include "e264_dev.h"
@@ -564,5 +565,222 @@ E264_DEV DkPlan dk_plan(int t, const DkRole &R, bool row_ok, bool top, int wm)
 // macroblocks of row g that have left for memory with the flush of step t (a publishing step)
 E264_DEV int dk_progress(int t, int g, int wm) { return min(max(((t - 1 - g) >> DK_LG) * DK_GS, 0), wm); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernels' bodies, one workgroup per picture (e264_kernels.hip wraps them).  A wave walks a GROUP of macroblock rows of kind K
+// (DkGeom: mixed 5 rows luma + chroma, luma-only 8 rows, chroma-only 16 rows) from left to right; it waits for the wave that walks
+// the group above through progress[] (macroblocks of that group's last row that have reached memory).
+#ifdef E264_WG_SYNC // (a host harness that brings no collectives of its own gets the phase functions and per-lane helpers only)
+// dk_walk_group: one group q of kind K, by the calling wave.  progress: the counters of this kind's chain of groups.
+template <int K>
+E264_DEV void dk_walk_group(DkWaveT<K> &W, const FrameCtx &f, int *progress, const int q, const int lane, const int tl_slot)
+{
+	typedef DkGeom<K> G;
+	const DkRole R = dk_role<K>(lane);
+	const int wm = f.wm, last_step = dk_last_step<K>(wm);
+	const int y0 = q * G::ROWS, y = y0 + R.g;
+	const bool row_ok = !R.idle && y < f.hm, top = q > 0;
+	const int lastg = min(G::ROWS, f.hm - y0) - 1; // the row the wave below waits for
+	const DkSrc src = dk_src<K>(f, R, y);
+#if defined(E264_PHASE_TIMING) || defined(E264_DBK_TIMELINE) // (device-only instrumentation: the one place a body looks at its workgroup's index)
+	if (blockIdx.x == 0 && lane == 0 && tl_slot < 64) g_timeline[2 * tl_slot] = __builtin_amdgcn_s_memtime();
+#endif
+	v4u tt = {0, 0, 0, 0};
+	DkRaw p0 = {{0, 0}, {0, 0}, {0, 0}}, p1 = p0; // the lane's parameter pieces: the set this step uses and the set it requests for the next one
+	v4u N[2 * DK_GS];       // samples of four (two) macroblocks of the lane's two rows (dk_fetch4), requested at steps t = 0 mod 4 (2)
+	v4u K2a = tt, K2b = tt, K3a = tt, K3b = tt; // the last two (groups of 2: K3, the last one) of them, kept while the next group is on its way
+	PH_DECL;
+	// one step; k = (t + 2) & 3: which macroblock of its group the step filters (k = 2, 3: of the group before, out of K2 / K3);
+	// groups of 2: k = t & 1, k = 1 out of K3, the step with k = 0 requests the next group;
+	// sp: the parameter pieces of x, requested by the step before; sn: where this step requests those of x + 1
+	auto step = [&](const int t, const int k, DkRaw &sp, DkRaw &sn) __attribute__((always_inline)) {
+		const DkPlan p = dk_plan(t, R, row_ok, top, wm);
+		// what earlier steps requested is picked up BEFORE this step's stores are issued: the compiler cannot count
+		// conditional stores, any use of a loaded register after them is an s_waitcnt vmcnt(0) = a full drain
+		if (p.top_commit >= 0) dk_top_commit<K>(W, f, lane, p.top_commit, y0, tt);
+		v4u ra, rb;
+		E264_PIN("v"(sp.v), "v"(sp.h), "v"(sp.w)); // (the parameters of this step have landed)
+		if (DK_GS == 4) {
+			if (k < 2) dk_pick<K>(N, R, k, ra, rb);
+			else { ra = k == 2 ? K2a : K3a; rb = k == 2 ? K2b : K3b; }
+			if (k == 1) { dk_pick<K>(N, R, 2, K2a, K2b); dk_pick<K>(N, R, 3, K3a, K3b); } // N is overwritten in the next step
+			E264_PIN("v"(ra), "v"(rb), "v"(K2a), "v"(K2b), "v"(K3a), "v"(K3b)); // the copies happen here
+		} else {
+			if (k == 0) { dk_pick<K>(N, R, 0, ra, rb); dk_pick<K>(N, R, 1, K3a, K3b); } // N is overwritten further down in this step
+			else { ra = K3a; rb = K3b; }
+			E264_PIN("v"(ra), "v"(rb), "v"(K3a), "v"(K3b));
+		}
+		if (p.flush >= 0) dk_flush<K>(W, f, R, p.flush, y);
+		if (p.top_flush >= 0) dk_top_flush<K>(W, f, lane, p.top_flush, y0);
+		PH(0);
+		if (p.top_fetch >= 0) { // (wave-uniform) the rows above this group of 4 must have reached memory
+			const int need = min(p.top_fetch * DK_GS + DK_GS, wm);
+#ifndef E264_ABL_DBK_NOWAIT // timing ablation: the group above is not waited for (wrong samples along the seams): what the hand-off lag costs
+			while (lds_load_relaxed(&progress[q - 1]) < need)
+				E264_SLEEP();
+#endif
+			E264_FENCE_ACQUIRE();
+			dk_top_fetch<K>(f, lane, p.top_fetch, y0, tt);
+		}
+		PH(1);
+		if (p.prm_fetch) dk_fetch_prm<K>(f, R, p.x + 1, y, sn);
+		if (k == (DK_GS == 4 ? 2 : 0) && p.grp_fetch) dk_fetch4<K>(src, R, p.x + 2, wm, N);
+		wave_sync();
+		PH(2);
+		DkPrm P[2];
+#if E264_DBK_ZEROSKIP // (wave-uniform) a step in which no macroblock of the wave has an edge to filter only moves its samples into the strips
+		if (!E264_ANY(p.act && dk_any_bs(sp) != 0)) {
+			E264_EMU_DBK_STEP(false);
+			if (p.act) dk_vcopy<K>(W, R, ra, rb, p.x);
+			wave_sync();
+		} else
+#endif
+		{
+			E264_EMU_DBK_STEP(true);
+			if (p.act) {
+				dk_params<K>(sp, R, P);
+				PH(3);
+				dk_vpass<K>(W, P[0], R, ra, rb, p.x);
+			}
+			wave_sync();
+			PH(4);
+			if (p.act) dk_hpass<K>(W, P[1], R, p.x);
+			wave_sync();
+		}
+		PH(5);
+		if (p.publish) {
+			// the stores at the top of this step must be visible to the wave below before the counter moves
+			E264_FENCE_RELEASE();
+			if (lane == lastg * G::LANES)
+				E264_PROGRESS_STORE(&progress[q], dk_progress(t, lastg, wm));
+		}
+		PH(6);
+	};
+#pragma unroll 1
+	for (int t = DK_FIRST_STEP; t <= last_step; t += DK_GS) { // unrolled by four (two): a group of macroblocks per fetch, registers by name
+		if (DK_GS == 4) {
+			step(t, 2, p0, p1);
+			step(t + 1, 3, p1, p0);
+			step(t + 2, 0, p0, p1);
+			step(t + 3, 1, p1, p0);
+		} else {
+			step(t, 0, p0, p1);
+			step(t + 1, 1, p1, p0);
+		}
+	}
+#if defined(E264_PHASE_TIMING) || defined(E264_DBK_TIMELINE)
+	if (blockIdx.x == 0 && lane == 0 && tl_slot < 64) g_timeline[2 * tl_slot + 1] = __builtin_amdgcn_s_memtime();
+#endif
+#ifndef E264_PHASE_INTRA
+	PH_FLUSH_DBK(lane);
+#endif
+}
+// the next task of a list that the workgroup's waves share through a counter in LDS
+E264_DEV int dk_take_task(int *next_task, int lane)
+{
+	int task = 0;
+	if (lane == 0) task = E264_TASK_TAKE(next_task);
+	return E264_FIRST(task);
+}
+
+// (a) mixed waves (rounds 2 and 3): NW waves take the groups of five rows round-robin
+template <int NW> struct DkLds { DkWaveT<2> lds[NW]; int progress[(E264_MAX_ROWS + DK_ROWS_OF(2) - 1) / DK_ROWS_OF(2)]; };
+template <int NW>
+E264_DEV void deblock_kernel_body(DkLds<NW> &S, const E264Job &job, const int tid)
+{
+	const int lane = tid & 63;
+	const int wave = E264_FIRST(tid >> 6);
+	FrameCtx f;
+	if (!open_frame(f, job) || !f.dbk)
+		return;
+	const int nquint = (f.hm + DK_ROWS_OF(2) - 1) / DK_ROWS_OF(2);
+	for (int i = tid; i < nquint; i += NW * 64)
+		S.progress[i] = 0;
+	E264_WG_SYNC();
+#pragma unroll 1
+	for (int q = wave; q < nquint; q += NW) {
+#ifndef E264_DBK_NO_PRIO // (1.045 - 1.059 -> 1.039 ms: profiles/r04_ablations.txt item 5)
+		// Groups of rows form ONE dependency chain (a wave waits for the group above), and two waves share a SIMD: with equal priority the
+		// OLDER wave wins the issue slots -- in its second pass (group w + NW) that is the wave whose work depends on its partner's
+		// first-pass group (w + NW / 2).  Earlier passes get the higher priority, whatever the wave's age.
+		{ const int pass = q / NW; if (pass == 0) E264_SETPRIO(3); else if (pass == 1) E264_SETPRIO(2); else if (pass == 2) E264_SETPRIO(1); else E264_SETPRIO(0); }
+#endif
+		dk_walk_group<2>(S.lds[wave], f, S.progress, q, lane, q);
+	}
+}
+
+// (b) luma waves and chroma waves (round 4).  Luma and chroma are two independent chains of groups (8 / 16 rows each); the NW waves
+// take the groups of BOTH chains from one list, luma and chroma interleaved in proportion, through a counter in LDS: a wave that
+// finishes takes the next group of the list, whatever its kind, so the SIMDs stay evenly loaded (the mixed kernel's 14 groups of a
+// 1080p picture fall 4 / 4 / 3 / 3 on the four SIMDs).  A group's predecessor is always earlier in the list: it has been taken.
+union DkWaveAny { DkWaveT<0> l; DkWaveT<1> c; };
+template <int NW> struct Dk2Lds {
+	DkWaveAny lds[NW];
+	int progress_l[(E264_MAX_ROWS + DK_ROWS_OF(0) - 1) / DK_ROWS_OF(0)], progress_c[(E264_MAX_ROWS + DK_ROWS_OF(1) - 1) / DK_ROWS_OF(1)], next_task;
+};
+#ifndef E264_DBK_ORDER
+#define E264_DBK_ORDER 0 // the task list: 0 = luma and chroma groups interleaved in proportion (round 4), 1 = all luma groups first, 2 = all chroma groups first
+#endif
+template <int NW>
+E264_DEV void deblock2_kernel_body(Dk2Lds<NW> &S, const E264Job &job, const int tid)
+{
+	const int lane = tid & 63;
+	const int wave = E264_FIRST(tid >> 6);
+	FrameCtx f;
+	if (!open_frame(f, job) || !f.dbk)
+		return;
+	const int nl = (f.hm + DK_ROWS_OF(0) - 1) / DK_ROWS_OF(0), nc = (f.hm + DK_ROWS_OF(1) - 1) / DK_ROWS_OF(1), total = nl + nc;
+	for (int i = tid; i < nl; i += NW * 64) S.progress_l[i] = 0;
+	for (int i = tid; i < nc; i += NW * 64) S.progress_c[i] = 0;
+	if (tid == 0) S.next_task = 0;
+	E264_WG_SYNC();
+#pragma unroll 1
+	for (;;) {
+		const int task = dk_take_task(&S.next_task, lane);
+		if (task >= total)
+			break;
+		if (E264_DBK_ORDER == 1) {
+			if (task < nl) dk_walk_group<0>(S.lds[wave].l, f, S.progress_l, task, lane, task);
+			else dk_walk_group<1>(S.lds[wave].c, f, S.progress_c, task - nl, lane, 32 + task - nl);
+		} else if (E264_DBK_ORDER == 2) {
+			if (task < nc) dk_walk_group<1>(S.lds[wave].c, f, S.progress_c, task, lane, 32 + task);
+			else dk_walk_group<0>(S.lds[wave].l, f, S.progress_l, task - nc, lane, task - nc);
+		} else {
+			// luma groups among the first i tasks of the list: (i * nl) / total; task i is a luma group iff that count grows at i + 1
+			const int lb = task * nl / total, la = (task + 1) * nl / total;
+			if (la > lb) dk_walk_group<0>(S.lds[wave].l, f, S.progress_l, lb, lane, lb);
+			else dk_walk_group<1>(S.lds[wave].c, f, S.progress_c, task - lb, lane, 32 + task - lb);
+		}
+	}
+}
+
+// The same walk with a picture's luma groups on one workgroup and its chroma groups on another: the two chains never meet (separate samples, the same
+// read-only parameters), so a picture that has the device to itself -- one stream, a small batch -- gets two CUs for the kernel that is most of its latency
+// (one workgroup per picture: 0.9 ms of a P picture's 0.9).  The planner's call (E264Plan.dbk = E264_DBK_PLANES: few pictures).
+template <int NW> struct DkPlanesLds {
+	DkWaveAny lds[NW];
+	int progress[(E264_MAX_ROWS + DK_ROWS_OF(0) - 1) / DK_ROWS_OF(0)], next_task; // (the longer of the two chains: luma groups are the shorter ones)
+};
+template <int NW>
+E264_DEV void deblock2_planes_kernel_body(DkPlanesLds<NW> &S, const E264Job &job, const bool chroma, const int tid)
+{
+	const int lane = tid & 63;
+	const int wave = E264_FIRST(tid >> 6);
+	FrameCtx f;
+	if (!open_frame(f, job) || !f.dbk)
+		return;
+	const int n = chroma ? (f.hm + DK_ROWS_OF(1) - 1) / DK_ROWS_OF(1) : (f.hm + DK_ROWS_OF(0) - 1) / DK_ROWS_OF(0);
+	for (int i = tid; i < n; i += NW * 64) S.progress[i] = 0;
+	if (tid == 0) S.next_task = 0;
+	E264_WG_SYNC();
+#pragma unroll 1
+	for (;;) {
+		const int task = dk_take_task(&S.next_task, lane);
+		if (task >= n)
+			break;
+		if (chroma) dk_walk_group<1>(S.lds[wave].c, f, S.progress, task, lane, 32 + task);
+		else dk_walk_group<0>(S.lds[wave].l, f, S.progress, task, lane, task);
+	}
+}
+#endif
 } // namespace
 #endif

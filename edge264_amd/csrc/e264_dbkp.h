@@ -29,7 +29,7 @@
 // Until round 5 every lane of the deblocking kernel derived these from the raw record in every step: ~26 LDS reads, a dependent tC0
 // table look-up and ~160 VALU instructions per step and wave, i.e. once per line-pair segment of each of the 8 (15) macroblocks of a step
 // AND per lane pair that shares it; here it is done once per macroblock by four threads.
-// The phases are plain functions of (LDS, frame, first macroblock, thread id): tests/emu runs them on the host.
+// The phases are plain functions of (LDS, frame, first macroblock, thread id); dbkparam2_body at the end is the kernel: tests/emu runs it on the host as it is.
 #ifndef E264_DBKP_H
 #define E264_DBKP_H
 #include "e264_dev.h"
@@ -371,5 +371,27 @@ template <class LDS> E264_DEV void dbkp_phase_store(const LDS &L, const FrameCtx
 	}
 }
 
+#ifdef E264_WG_SYNC // (a host harness that brings no collectives of its own gets the phase functions and per-lane helpers only)
+// what thread tid of the workgroup of macroblocks a0 .. a0 + DP_MBS - 1 does
+template <bool HAS_L1>
+E264_DEV void dbkparam2_body(DbkpLdsT<HAS_L1> &L, const E264Job &job, const int a0, const int tid)
+{
+	FrameCtx f;
+	if (!open_frame(f, job) || !f.dbk || a0 >= f.wm * f.hm)
+		return;
+	dbkp_phase_load(L, f, a0, tid);
+	E264_WG_SYNC();
+	dbkp_phase_slices(L, f, tid);
+	E264_WG_SYNC();
+	dbkp_phase_compute(L, f, a0, tid);
+	E264_WG_SYNC();
+	E264_EMU_DBKP_RAW(L, f, a0);
+#ifndef E264_ABL_DBKP_NOPIECES // timing ablation: the pieces are not built (whatever the LDS holds is written)
+	dbkp_phase_pieces(L, tid);
+#endif
+	E264_WG_SYNC();
+	dbkp_phase_store(L, f, a0, tid);
+}
+#endif
 } // namespace
 #endif

@@ -1,10 +1,10 @@
 // e264_dev.h -- device-side definitions shared by the gfx950 kernels (e264_kernels.hip, e264_pred.h):
 // address-space pointer types, small integer helpers, the spec tables, FrameCtx / open_frame.
 //
-// The kernels' source is also compiled for the HOST by the test suite (tests/emu/: every thread of a workgroup is run
-// phase by phase by a plain C++ loop and the result is compared with the CPU oracle before any GPU time is spent).  That
-// build pre-defines the three hooks below (qualifiers, address spaces, the handful of byte-permute intrinsics); the
-// product build never does.
+// The kernels' source is also compiled for the HOST by the test suite (tests/emu/: every thread of a workgroup is a fibre
+// that runs its kernel's body as it is and meets the others at the collectives below; the result is compared with the CPU
+// oracle before any GPU time is spent).  That build pre-defines the hooks below (qualifiers, address spaces, the handful of
+// byte-permute intrinsics, the collectives); the product build never does.
 #ifndef E264_DEV_H
 #define E264_DEV_H
 #include <stdint.h>
@@ -20,8 +20,52 @@
 #define E264_AS_CONST __attribute__((address_space(4)))
 #endif
 
+// ---- what the source assumes about a wave and a workgroup: threads meet at these and communicate through LDS across them only ----
+#ifndef E264_HOST_INTRINSICS
+#define E264_FIRST(x) __builtin_amdgcn_readfirstlane(x)          // a value every lane of the wave holds, as a scalar
+#define E264_BALLOT(x) __ballot(x)
+#define E264_ANY(x) __any(x)
+#define E264_WG_SYNC() __syncthreads()
+#define E264_WG_OR(x) __syncthreads_or(x)
+#define E264_SLEEP() __builtin_amdgcn_s_sleep(1)
+#define E264_FENCE_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup")
+#define E264_FENCE_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup")
+#define E264_PROGRESS_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define E264_PROGRESS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define E264_ROW_TAKE(p) __hip_atomic_fetch_add((p), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define E264_TASK_TAKE(p) atomicAdd((p), 1)
+#define E264_SETPRIO(n) __builtin_amdgcn_s_setprio(n)
+#define E264_PIN(...) asm volatile("" :: __VA_ARGS__)              // the named registers hold their values HERE (operands as in an asm statement)
+// what the host build looks at between two phases of a body (tests/emu/pred_emu.cpp): nothing on the device
+#define E264_EMU_DBKP_RAW(L, f, a0)
+#define E264_EMU_DBK_STEP(filtered)
+#endif
+#define E264_MAX_ROWS 1056
+
 namespace {
 
+// -DE264_PHASE_TIMING: wall cycles of a kernel's phases, summed over all waves (tools/visits/gpu_phase.sh reads them back
+// through e264_debug_phase_cycles).  s_memtime at the phase boundaries drains the LGKM counter, so the numbers are a
+// profile, not a benchmark.
+#if defined(E264_DBK_TIMELINE) || defined(E264_PHASE_TIMING) // (-DE264_DBK_TIMELINE alone: only the start / end stamps of the deblocking kernel's groups of rows, two s_memtime per 130 steps)
+__device__ unsigned long long g_phase[32]; // [0..13] mbpar kernel, [16..29] deblock kernel
+__device__ unsigned long long g_timeline[128]; // deblock kernel, workgroup 0: start / end of every group of five rows
+#endif
+#ifdef E264_PHASE_TIMING
+#define PH_DECL unsigned long long ph_t = __builtin_amdgcn_s_memtime(), ph_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define PH(k) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); ph_acc[k] += t_ - ph_t; ph_t = t_; } while (0)
+#define PH_FLUSH(lane) do { if ((lane) == 0) for (int k_ = 0; k_ < 14; k_++) atomicAdd(&g_phase[k_], ph_acc[k_]); } while (0)
+#define PH_FLUSH_DBK(lane) do { if ((lane) == 0) for (int k_ = 0; k_ < 14; k_++) atomicAdd(&g_phase[16 + k_], ph_acc[k_]); } while (0)
+#define PH_PARAMS , unsigned long long &ph_t, unsigned long long (&ph_acc)[14]
+#define PH_ARGS , ph_t, ph_acc
+#else
+#define PH_DECL
+#define PH(k)
+#define PH_FLUSH(lane)
+#define PH_FLUSH_DBK(lane)
+#define PH_PARAMS
+#define PH_ARGS
+#endif
 
 // ---------------------------------------------------------------------------------
 // small helpers
@@ -69,6 +113,7 @@ E264_DEV void wave_sync()
 	__builtin_amdgcn_wave_barrier();
 }
 #endif
+#define lds_load_relaxed(p) E264_PROGRESS_LOAD(p)
 
 __constant__ uint8_t c_BX[16] = {0, 4, 0, 4, 8, 12, 8, 12, 0, 4, 0, 4, 8, 12, 8, 12};
 __constant__ uint8_t c_BY[16] = {0, 0, 4, 4, 0, 0, 4, 4, 8, 8, 12, 12, 8, 8, 12, 12};

@@ -6,22 +6,11 @@
 //
 // The whole kernel lives here (moved out of e264_kernels.hip in round 3) so that tests/emu can compile it for the HOST as it
 // is: the 64 lanes of a wave run as 64 fibres that meet at the collectives (wave_sync, E264_BALLOT, E264_FIRST), the wavefront of
-// rows is one wave taking the rows in order (tests/emu/intra_emu.cpp, tests/test_intra_emu.py).  The hooks below are the
-// only difference between the two builds.
+// rows is one wave taking the rows in order (tests/emu/intra_emu.cpp, tests/test_intra_emu.py).  The collectives of e264_dev.h
+// are the only difference between the two builds.
 #ifndef E264_INTRA_H
 #define E264_INTRA_H
 #include "e264_dev.h"
-
-#ifndef E264_HOST_INTRINSICS
-#define E264_FIRST(x) __builtin_amdgcn_readfirstlane(x)          // a value every lane of the wave holds, as a scalar
-#define E264_BALLOT(x) __ballot(x)
-#define E264_WG_SYNC() __syncthreads()
-#define E264_SLEEP() __builtin_amdgcn_s_sleep(1)
-#define E264_FENCE_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup")
-#define E264_FENCE_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup")
-#define E264_PROGRESS_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define E264_PROGRESS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#endif
 
 namespace {
 #ifndef E264_HOST_INTRINSICS
@@ -747,13 +736,6 @@ E264_DEV void recon_mb(WaveLds &L, const FrameCtx &f, const MbInfo &m, int mbx, 
 // ---------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------
-E264_DEV int lds_load_relaxed(const int *p)
-{
-	return E264_PROGRESS_LOAD(p);
-}
-
-
-#define E264_MAX_ROWS 1056
 // A row may reconstruct macroblock x once the row above has finished x + 1: rows that start the moment they may run exactly two
 // macroblocks behind each other, with no slack -- whenever any row of the wavefront is late (a slower kind of macroblock, a lost
 // arbitration) every row below it waits, and the picture advances at the pace of the slowest row of each step.  A row's FIRST
@@ -779,9 +761,6 @@ struct __attribute__((aligned(16))) IntraLds {
 // the row a wave may have to wait for (y - 1) has always been taken by somebody: no deadlock.
 #ifndef E264_INTRA_DYNROWS
 #define E264_INTRA_DYNROWS 1
-#endif
-#ifndef E264_ROW_TAKE
-#define E264_ROW_TAKE(p) __hip_atomic_fetch_add((p), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #endif
 template <int NW>
 E264_DEV int intra_next_row(int *next_row, int y, int lane)

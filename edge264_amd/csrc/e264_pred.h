@@ -30,8 +30,9 @@
 //     transform of every coded macroblock with a quarter of its lanes busy).
 //
 // The kernel is a sequence of PHASES separated by workgroup barriers; threads only communicate through LDS between
-// phases.  Each phase is a plain function of (LDS, frame, tile, thread id): tests/emu/ compiles this very file for the
-// host, runs the phases thread by thread and compares the tile with the CPU oracle (tests/test_pred_emu.py).
+// phases.  Each phase is a plain function of (LDS, frame, tile, thread id), pred_kernel_body at the end is their sequence:
+// tests/emu/ compiles this very file for the host, runs the body as it is, one fibre per thread, and compares the tile
+// with the CPU oracle (tests/test_pred_emu.py).
 #ifndef E264_PRED_H
 #define E264_PRED_H
 #include "e264_dev.h"
@@ -1238,5 +1239,57 @@ E264_DEV void pred_phase_flush(const PredLds &L, const FrameCtx &f, const PredTi
 	}
 }
 
+#ifdef E264_WG_SYNC // (a host harness that brings no collectives of its own gets the phase functions and per-lane helpers only)
+// what thread tid of the workgroup of tile bx (of the picture's tiles in raster order) does
+E264_DEV void pred_kernel_body(PredLds &L, const E264Job &job, const int bx, const int tid)
+{
+	FrameCtx f;
+	if (!open_frame(f, job))
+		return;
+	const int ntx = (f.wm + PT_W - 1) / PT_W, nty = (f.hm + PT_H - 1) / PT_H;
+	if (bx >= ntx * nty)
+		return;
+	const PredTile t = {(bx % ntx) * PT_W, (bx / ntx) * PT_H};
+	PH_DECL;
+	pred_phase_setup(L, f, t, tid);
+	PH(0);
+	E264_WG_SYNC();
+	pred_phase_bitmap(L, f, t, tid);
+	{ // nothing more for this kernel in the tile (every tile of an I frame)? leave at once
+		const int kind = tid < PT_MBS ? (int)(L.hdr[tid][0] & 255) : 0;
+		if (!E264_WG_OR(kind == E264_MB_INTER || kind == E264_MB_PCM))
+			return;
+	}
+	PH(1);
+	pred_phase_classify(L, f, t, 0, tid);
+	PH(2);
+	E264_WG_SYNC();
+	PH(3);
+	pred_phase_items(L, f, t, 0, tid);
+	PH(4);
+	E264_WG_SYNC();
+	PH(5);
+	if (L.any_l1) { // uniform: written before the barrier above
+		pred_phase_reset(L, tid);
+		E264_WG_SYNC();
+		pred_phase_classify(L, f, t, 1, tid);
+		E264_WG_SYNC();
+		pred_phase_items(L, f, t, 1, tid);
+		E264_WG_SYNC();
+	}
+	PH(6);
+	pred_phase_reslist(L, tid);
+	PH(7);
+	E264_WG_SYNC();
+	PH(8);
+	pred_phase_residual(L, f, tid);
+	PH(9);
+	E264_WG_SYNC();
+	PH(10);
+	pred_phase_flush(L, f, t, tid);
+	PH(11);
+	PH_FLUSH(tid & 63);
+}
+#endif
 } // namespace
 #endif

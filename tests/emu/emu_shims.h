@@ -1,9 +1,9 @@
 // tests/emu/emu_shims.h -- TEST INFRASTRUCTURE: what the kernels' source needs to compile for the host (qualifiers, address spaces,
-// the VALU byte instructions the source names, LDS atomics of a sequentially emulated workgroup).  Shared by pred_emu.cpp and intra_emu.cpp.
+// the VALU byte instructions the source names, LDS atomics and the collectives of a workgroup whose threads are fibres: emu_fibres.h).
+// Shared by pred_emu.cpp and intra_emu.cpp.
 #ifndef E264_EMU_SHIMS_H
 #define E264_EMU_SHIMS_H
-#include <stdint.h>
-#include <string.h>
+#include "emu_fibres.h"
 #define E264_HOST_INTRINSICS
 #define E264_DEV static inline
 #define E264_AS_GLOBAL
@@ -40,6 +40,21 @@ static inline uint32_t v_sat_pk_u8_i16(uint32_t v)
 	a = a < 0 ? 0 : a > 255 ? 255 : a; b = b < 0 ? 0 : b > 255 ? 255 : b;
 	return (uint32_t)a | (uint32_t)b << 8;
 }
-static inline int lds_add(int *p, int v) { int o = *p; *p += v; return o; }
+static inline int lds_add(int *p, int v) { int o = *p; *p += v; return o; } // (fibres switch inside the collectives only)
 static inline void lds_or(uint32_t *p, uint32_t v) { *p |= v; }
+// the host side of e264_dev.h's collectives.  A workgroup that shares a list of rows / groups is ONE wave here (NW = 1) that takes them in order: what it would wait for is done
+#define E264_FIRST(x) ((__typeof__((x) + 0))emu_first((uint32_t)(x)))
+#define E264_BALLOT(x) emu_ballot(x)
+#define E264_ANY(x) (emu_ballot(x) != 0)
+#define E264_WG_SYNC() emu_wg_sync()
+#define E264_WG_OR(x) emu_wg_or(x)
+#define E264_SLEEP() (fprintf(stderr, "emu: a wave waits for the row or group above: impossible with one wave taking them in order\n"), abort())
+#define E264_FENCE_ACQUIRE() do { } while (0)
+#define E264_FENCE_RELEASE() do { } while (0)
+#define E264_PROGRESS_STORE(p, v) (*(p) = (v))
+#define E264_PROGRESS_LOAD(p) (*(p))
+#define E264_ROW_TAKE(p) ((*(p))++)                 /* (never reached: one wave takes the rows in order, intra_next_row's NW == 1 path) */
+#define E264_TASK_TAKE(p) ((*(p))++)
+#define E264_SETPRIO(n) do { } while (0)
+#define E264_PIN(...) do { } while (0)
 #endif

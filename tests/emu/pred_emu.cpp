@@ -1,12 +1,25 @@
-// tests/emu/pred_emu.cpp -- TEST INFRASTRUCTURE.  Compiles the product's kernel source (edge264_amd/csrc/e264_pred.h) for
-// the host and runs e264_pred_kernel's phases thread by thread, tile by tile: the same arithmetic, the same LDS layout,
-// the same work lists, with the four VALU byte instructions the source names restated below.  tests/test_pred_emu.py
-// compares the result with the CPU oracle, so that a logic error is found here and not on the GPU box.
-#include <stdlib.h>
+// tests/emu/pred_emu.cpp -- TEST INFRASTRUCTURE.  Compiles the product's kernel source (edge264_amd/csrc/e264_pred.h, e264_dbkp.h,
+// e264_dbk.h, e264_expand.h) for the host and runs the kernels' BODIES as they are, workgroup by workgroup: every thread is a
+// fibre (emu_fibres.h) that meets the others at the barriers and collectives the source names -- the same arithmetic, the same
+// LDS layout, the same schedule, with the VALU byte instructions restated in emu_shims.h.  tests/test_pred_emu.py, test_dbkp_emu.py
+// and test_dbk_emu.py compare the results with the CPU oracle, so that a logic error is found here and not on the GPU box.
+// The two places where a test looks into a body between its phases (empty on the device, e264_dev.h):
+//   the parameter kernel's raw records, as they stand in LDS once they are computed; the motion area the pieces then reuse is poisoned (nothing of it may be read any more)
+#define E264_EMU_DBKP_RAW(L, f, a0) do { if (g_cur == 0) { \
+		if (g_raw) for (int i_ = 0; i_ < DP_MBS && (a0) + i_ < (f).wm * (f).hm; i_++) memcpy(g_raw + (size_t)((a0) + i_) * DP_RAW, (L).out[i_], DP_RAW); \
+		memset((L).mo, 0xA5, sizeof((L).mo)); } \
+	emu_wg_sync(); } while (0)
+//   the deblocking steps that took the filter path / the copy-only path (tests check that both are exercised)
+#define E264_EMU_DBK_STEP(filtered) do { if ((g_cur & 63) == 0) ((filtered) ? g_filter_steps : g_zero_steps)++; } while (0)
 #include "emu_shims.h"
+static uint8_t *g_raw;
+static long g_zero_steps, g_filter_steps;
 #include "../../edge264_amd/csrc/e264_pred.h"
 #include "../../edge264_amd/csrc/e264_dbkp.h"
+#include "../../edge264_amd/csrc/e264_dbk.h"
 #include "../../edge264_amd/csrc/e264_expand.h"
+static const E264Job *g_job; // what the workgroup being run is given: its job, and its tile / first macroblock
+static int g_wg_arg;
 
 // e264_expand_kernel over one wire packet (include/edge264_compact.h) with a grid of nt threads: area = e264_expand_area_bytes(wire)
 extern "C" __attribute__((visibility("default"))) int e264emu_expand(const uint8_t *wire, uint8_t *area, int nt)
@@ -26,36 +39,18 @@ extern "C" __attribute__((visibility("default"))) int e264emu_pred_frame2(const 
 	if (!open_frame(f, job))
 		return -1;
 	static PredLds L;
+	g_job = &job;
 	const int ntx = (f.wm + PT_W - 1) / PT_W, nty = (f.hm + PT_H - 1) / PT_H;
-	for (int ti = 0; ti < ntx * nty; ti++) {
-		PredTile t = {(ti % ntx) * PT_W, (ti / ntx) * PT_H};
+	for (g_wg_arg = 0; g_wg_arg < ntx * nty; g_wg_arg++) {
 		memset(&L, 0xA5, sizeof(L)); // LDS is not zeroed on the device either
-		for (int tid = 0; tid < PT_NT; tid++) pred_phase_setup(L, f, t, tid);
-		for (int tid = 0; tid < PT_NT; tid++) pred_phase_bitmap(L, f, t, tid);
-		for (int list = 0; list < 2; list++) {
-			if (list == 1 && !L.any_l1) break;
-			if (list == 1) for (int tid = 0; tid < PT_NT; tid++) pred_phase_reset(L, tid);
-			for (int tid = 0; tid < PT_NT; tid++) pred_phase_classify(L, f, t, list, tid);
-			for (int tid = 0; tid < PT_NT; tid++) pred_phase_items(L, f, t, list, tid);
-		}
-		for (int tid = 0; tid < PT_NT; tid++) pred_phase_reslist(L, tid);
-		for (int tid = 0; tid < PT_NT; tid++) pred_phase_residual(L, f, tid);
-		for (int tid = 0; tid < PT_NT; tid++) pred_phase_flush(L, f, t, tid);
+		emu_run_workgroup(PT_NT, [](int tid) { pred_kernel_body(L, *g_job, g_wg_arg, tid); });
 	}
 	return 0;
 }
+extern "C" __attribute__((visibility("default"))) int e264emu_pred_frame(const uint8_t *pkt, uint8_t *const *dpb) { return e264emu_pred_frame2(pkt, dpb, nullptr); }
 
-extern "C" __attribute__((visibility("default"))) int e264emu_pred_frame(const uint8_t *pkt, uint8_t *const *dpb)
-{
-	return e264emu_pred_frame2(pkt, dpb, nullptr);
-}
-
-// e264_dbkparam2_kernel: out = E264_DBK_BYTES (256) per macroblock, the pieces of the deblocking lanes' layout; raw (may be NULL) = the 64-byte
+// e264_dbkparam2_kernel: out = E264_DBK_BYTES per macroblock, the pieces of the deblocking lanes' layout; raw (may be NULL) = the 64-byte
 // raw records (bS, alpha, beta, indexA) the pieces are made of, as they stand in LDS between the kernel's phases
-template <bool HAS_L1> static int emu_dbkparam(const uint8_t *pkt, uint8_t *out, uint8_t *raw);
-extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame2(const uint8_t *pkt, uint8_t *out, uint8_t *raw) { return emu_dbkparam<true>(pkt, out, raw); }
-// the kernel's small form (no room for list 1 in LDS): for pictures that do not predict from list 1 only -- the launcher's choice on the device
-extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame2_nol1(const uint8_t *pkt, uint8_t *out, uint8_t *raw) { return emu_dbkparam<false>(pkt, out, raw); }
 template <bool HAS_L1> static int emu_dbkparam(const uint8_t *pkt, uint8_t *out, uint8_t *raw)
 {
 	uint8_t dummy = 0;
@@ -66,35 +61,23 @@ template <bool HAS_L1> static int emu_dbkparam(const uint8_t *pkt, uint8_t *out,
 	if (!open_frame(f, job))
 		return -1;
 	static DbkpLdsT<HAS_L1> L;
-	const int n = f.wm * f.hm;
-	for (int a0 = 0; a0 < n; a0 += DP_MBS) {
+	g_job = &job; g_raw = raw;
+	for (g_wg_arg = 0; g_wg_arg < f.wm * f.hm; g_wg_arg += DP_MBS) {
 		memset(&L, 0xA5, sizeof(L));
-		for (int tid = 0; tid < DP_NT; tid++) dbkp_phase_load(L, f, a0, tid);
-		for (int tid = 0; tid < DP_NT; tid++) dbkp_phase_slices(L, f, tid);
-		for (int tid = 0; tid < DP_NT; tid++) dbkp_phase_compute(L, f, a0, tid);
-		if (raw) for (int i = 0; i < DP_MBS && a0 + i < n; i++) memcpy(raw + (size_t)(a0 + i) * DP_RAW, L.out[i], DP_RAW);
-		memset(L.mo, 0xA5, sizeof(L.mo)); // (the pieces reuse the motion area: nothing of it may be read any more)
-		for (int tid = 0; tid < DP_NT; tid++) dbkp_phase_pieces(L, tid);
-		for (int tid = 0; tid < DP_NT; tid++) dbkp_phase_store(L, f, a0, tid);
+		emu_run_workgroup(DP_NT, [](int tid) { dbkparam2_body<HAS_L1>(L, *g_job, g_wg_arg, tid); });
 	}
 	return 0;
 }
+extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame2(const uint8_t *pkt, uint8_t *out, uint8_t *raw) { return emu_dbkparam<true>(pkt, out, raw); }
+// the kernel's small form (no room for list 1 in LDS): for pictures that do not predict from list 1 only -- the launcher's choice on the device
+extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame2_nol1(const uint8_t *pkt, uint8_t *out, uint8_t *raw) { return emu_dbkparam<false>(pkt, out, raw); }
 // the pieces alone: what e264emu_deblock_frame2 consumes
-extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame(const uint8_t *pkt, uint8_t *out)
-{
-	return e264emu_dbkparam_frame2(pkt, out, nullptr);
-}
+extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_frame(const uint8_t *pkt, uint8_t *out) { return e264emu_dbkparam_frame2(pkt, out, nullptr); }
 // the raw records alone (64 bytes per macroblock)
 extern "C" __attribute__((visibility("default"))) int e264emu_dbkparam_raw(const uint8_t *pkt, uint8_t *raw)
 {
-	FrameCtx f;
-	uint8_t dummy = 0;
-	uint8_t *dpb[E264_MAX_SLOTS];
-	for (int i = 0; i < E264_MAX_SLOTS; i++) dpb[i] = &dummy;
-	E264Job job = {pkt, dpb, &dummy, g_expand};
-	if (!open_frame(f, job))
-		return -1;
-	uint8_t *out = (uint8_t *)malloc((size_t)f.wm * f.hm * E264_DBK_BYTES);
+	const E264FrameHdr *h = (const E264FrameHdr *)pkt; // (vetted by open_frame in e264emu_dbkparam_frame2; a macroblock count is at most 16 bits each way)
+	uint8_t *out = (uint8_t *)malloc((size_t)h->width_mbs * h->height_mbs * E264_DBK_BYTES + 1);
 	const int r = e264emu_dbkparam_frame2(pkt, out, raw);
 	free(out);
 	return r;
@@ -115,89 +98,35 @@ extern "C" __attribute__((visibility("default"))) void e264emu_dbk_pieces(const 
 }
 extern "C" __attribute__((visibility("default"))) int e264emu_dbk_bytes(void) { return E264_DBK_BYTES; }
 
-// e264_deblock_kernel / e264_deblock2_kernel: dbk = the parameter records (e264emu_dbkparam_frame's output); the picture in
-// dpb[dst_slot] is filtered in place.  Groups of rows are run one after the other (a group only ever waits for the group above it
-// of its own kind), the lanes of a wave phase by phase.  K: the kind of wave (DkGeom): 2 mixed, 0 luma only, 1 chroma only.
-#include "../../edge264_amd/csrc/e264_dbk.h"
-static long g_zero_steps, g_filter_steps; // steps that took the copy-only path / the filter path (tests check that both are exercised)
+// e264_deblock_kernel / e264_deblock2_kernel / e264_deblock2_planes_kernel: dbk = the parameter records (e264emu_dbkparam_frame's output);
+// the picture in dpb[dst_slot] is filtered in place by the kernel's body with ONE wave (NW = 1), which takes the groups of rows in the
+// order of the kernel's list: the group a group waits for (the one above it, of its own kind) is always done.
 extern "C" __attribute__((visibility("default"))) void e264emu_deblock_step_counts(long *zero, long *filt, int reset)
 {
 	*zero = g_zero_steps; *filt = g_filter_steps;
 	if (reset) g_zero_steps = g_filter_steps = 0;
 }
-template <int K>
-static void emu_walk_group(const FrameCtx &f, int q)
-{
-	typedef DkGeom<K> G;
-	static DkWaveT<K> W;
-	DkRole R[64];
-	for (int lane = 0; lane < 64; lane++) R[lane] = dk_role<K>(lane);
-	memset(&W, 0xA5, sizeof(W));
-	const int y0 = q * G::ROWS;
-	const bool top = q > 0;
-	static v4u N[64][2 * DK_GS], K2a[64], K2b[64], K3a[64], K3b[64], tt[64], ra[64], rb[64];
-	static DkRaw np[2][64];
-	memset(N, 0x5A, sizeof(N)); memset(K2a, 0x5A, sizeof(K2a)); memset(K2b, 0x5A, sizeof(K2b)); memset(K3a, 0x5A, sizeof(K3a)); memset(K3b, 0x5A, sizeof(K3b));
-	memset(np, 0x5A, sizeof(np)); memset(tt, 0x5A, sizeof(tt));
-	for (int t4 = DK_FIRST_STEP; t4 <= dk_last_step<K>(f.wm); t4 += DK_GS) // (the kernel's loop: whole groups of four (two) steps)
-	for (int t = t4; t < t4 + DK_GS; t++) {
-		const int par = t & 1, k = (t + 2) & (DK_GS - 1); // the parameter register set of this step; which macroblock of its group it filters
-		DkPlan p[64];
-		for (int lane = 0; lane < 64; lane++) {
-			const int y = y0 + R[lane].g;
-			p[lane] = dk_plan(t, R[lane], !R[lane].idle && y < f.hm, top, f.wm);
-			if (p[lane].top_commit >= 0) dk_top_commit<K>(W, f, lane, p[lane].top_commit, y0, tt[lane]);
-			if (DK_GS == 4) {
-				if (k < 2) dk_pick<K>(N[lane], R[lane], k, ra[lane], rb[lane]);
-				else { ra[lane] = k == 2 ? K2a[lane] : K3a[lane]; rb[lane] = k == 2 ? K2b[lane] : K3b[lane]; }
-				if (k == 1) { dk_pick<K>(N[lane], R[lane], 2, K2a[lane], K2b[lane]); dk_pick<K>(N[lane], R[lane], 3, K3a[lane], K3b[lane]); }
-			} else if (k == 0) { dk_pick<K>(N[lane], R[lane], 0, ra[lane], rb[lane]); dk_pick<K>(N[lane], R[lane], 1, K3a[lane], K3b[lane]); }
-			else { ra[lane] = K3a[lane]; rb[lane] = K3b[lane]; }
-			if (p[lane].flush >= 0) dk_flush<K>(W, f, R[lane], p[lane].flush, y);
-			if (p[lane].top_flush >= 0) dk_top_flush<K>(W, f, lane, p[lane].top_flush, y0);
-			if (p[lane].top_fetch >= 0) dk_top_fetch<K>(f, lane, p[lane].top_fetch, y0, tt[lane]);
-			if (p[lane].prm_fetch) dk_fetch_prm<K>(f, R[lane], p[lane].x + 1, y, np[par ^ 1][lane]);
-			if (k == (DK_GS == 4 ? 2 : 0) && p[lane].grp_fetch) dk_fetch4<K>(dk_src<K>(f, R[lane], y), R[lane], p[lane].x + 2, f.wm, N[lane]);
-		}
-		static DkPrm P[64][2];
-		bool any_edge = !E264_DBK_ZEROSKIP; // (the kernel's wave-uniform test: no macroblock of the wave has an edge to filter -> samples only move into the strips)
-		for (int lane = 0; lane < 64; lane++)
-			if (p[lane].act && dk_any_bs(np[par][lane]) != 0) any_edge = true;
-		if (!any_edge) {
-			for (int lane = 0; lane < 64; lane++)
-				if (p[lane].act) dk_vcopy<K>(W, R[lane], ra[lane], rb[lane], p[lane].x);
-			g_zero_steps++;
-			continue;
-		}
-		g_filter_steps++;
-		for (int lane = 0; lane < 64; lane++)
-			if (p[lane].act) {
-				dk_params<K>(np[par][lane], R[lane], P[lane]);
-				dk_vpass<K>(W, P[lane][0], R[lane], ra[lane], rb[lane], p[lane].x);
-			}
-		for (int lane = 0; lane < 64; lane++)
-			if (p[lane].act) dk_hpass<K>(W, P[lane][1], R[lane], p[lane].x);
-	}
-}
-// split: 0 = mixed waves (e264_deblock_kernel), 1 = luma waves + chroma waves (e264_deblock2_kernel)
+// split: 0 = mixed waves (e264_deblock_kernel), 1 = luma waves + chroma waves (e264_deblock2_kernel),
+// 2 = e264_deblock2_planes_kernel's two workgroups one after the other, chroma FIRST (the two never read each other's samples)
 extern "C" __attribute__((visibility("default"))) int e264emu_deblock_frame2(const uint8_t *pkt, uint8_t *const *dpb, uint8_t *dbk, int split)
 {
 	E264Job job = {pkt, dpb, dbk, g_expand};
 	FrameCtx f;
 	if (!open_frame(f, job) || !f.dbk)
 		return -1;
-	if (!split) {
-		for (int q = 0; q < (f.hm + DK_ROWS_OF(2) - 1) / DK_ROWS_OF(2); q++) emu_walk_group<2>(f, q);
-	} else {
-		for (int q = 0; q < (f.hm + DK_ROWS_OF(1) - 1) / DK_ROWS_OF(1); q++) emu_walk_group<1>(f, q); // (the two chains are independent: any order)
-		for (int q = 0; q < (f.hm + DK_ROWS_OF(0) - 1) / DK_ROWS_OF(0); q++) emu_walk_group<0>(f, q);
+	static union { DkLds<1> mixed; Dk2Lds<1> two; DkPlanesLds<1> planes; } S;
+	g_job = &job;
+	memset(&S, 0xA5, sizeof(S));
+	if (split == 0) emu_run_workgroup(64, [](int tid) { deblock_kernel_body<1>(S.mixed, *g_job, tid); });
+	else if (split == 1) emu_run_workgroup(64, [](int tid) { deblock2_kernel_body<1>(S.two, *g_job, tid); });
+	else {
+		emu_run_workgroup(64, [](int tid) { deblock2_planes_kernel_body<1>(S.planes, *g_job, true, tid); });
+		memset(&S, 0xA5, sizeof(S));
+		emu_run_workgroup(64, [](int tid) { deblock2_planes_kernel_body<1>(S.planes, *g_job, false, tid); });
 	}
 	return 0;
 }
-extern "C" __attribute__((visibility("default"))) int e264emu_deblock_frame(const uint8_t *pkt, uint8_t *const *dpb, uint8_t *dbk)
-{
-	return e264emu_deblock_frame2(pkt, dpb, dbk, 0);
-}
+extern "C" __attribute__((visibility("default"))) int e264emu_deblock_frame(const uint8_t *pkt, uint8_t *const *dpb, uint8_t *dbk) { return e264emu_deblock_frame2(pkt, dpb, dbk, 0); }
 
 // the four edge slots of one lane: lines[2][20] (positions -4..15 of the lane's two lines) filtered in place; prm: a RAW 64-byte record
 extern "C" __attribute__((visibility("default"))) void e264emu_dk_filter(uint8_t *lines, const uint8_t *prm, int lane, int dir)

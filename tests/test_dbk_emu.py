@@ -1,5 +1,6 @@
-"""e264_deblock_kernel's source run on the HOST (tests/emu) against the CPU oracle: the picture the oracle reconstructs
-without deblocking goes through the parameter kernel's and the filter kernel's phases, lane by lane, and must come out as
+"""The deblocking kernels' source run on the HOST (tests/emu) against the CPU oracle: the picture the oracle reconstructs
+without deblocking goes through the parameter kernel's body and the body of each of the three filter kernels (one wave of 64
+fibres that takes the groups of rows in the kernel's list order), and must come out as
 the oracle's deblocked picture -- every macroblock kind, bS 0..4, both transforms, slices with deblocking off / across
 slice edges off, filter offsets, frames narrower than a group of 4 and taller than one wave's five rows."""
 import ctypes as C
@@ -59,7 +60,7 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("split", [0, 1], ids=["mixed_waves", "luma_and_chroma_waves"])
+@pytest.mark.parametrize("split", [0, 1, 2], ids=["mixed_waves", "luma_and_chroma_waves", "luma_and_chroma_workgroups"])
 @pytest.mark.parametrize("name,gop,w,h,kw", CASES, ids=[c[0] for c in CASES])
 def test_deblock_emu(emu, name, gop, w, h, kw, split):
     g = synth.StreamSynth(w, h, seed=len(name) * 7 + 1, **kw)

@@ -1,4 +1,4 @@
-"""e264_dbkparam2_kernel's source run on the HOST (tests/emu): bS against the oracle's derivation (edge264_deblock.c:958-1118),
+"""e264_dbkparam2_kernel's body run on the HOST as it is (tests/emu: a workgroup's 256 threads as fibres that meet at the barriers): bS against the oracle's derivation (edge264_deblock.c:958-1118),
 alpha / beta / indexA against a direct restatement of edge264_deblock.c:945-955, on frames with every macroblock kind,
 multiple slices, all deblocking modes and filter offsets.  The -m gpu tests cover the same kernel through whole-frame parity."""
 import ctypes as C

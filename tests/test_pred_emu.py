@@ -1,4 +1,4 @@
-"""e264_pred_kernel's source run on the HOST (tests/emu) against the CPU oracle: every inter / PCM macroblock of synthetic
+"""e264_pred_kernel's body run on the HOST as it is (tests/emu: a tile's 256 threads as fibres that meet at the barriers) against the CPU oracle: every inter / PCM macroblock of synthetic
 P and B frames (all partition shapes, all 16 quarter-sample positions, vectors far outside the frame, both transforms,
 scaling lists, every weighting scheme, PCM, multiple slices).  Finds logic errors without a GPU; the -m gpu tests run the
 same comparison through the C-ABI on the device."""
