@@ -29,6 +29,9 @@
 // Until round 5 every lane of the deblocking kernel derived these from the raw record in every step: ~26 LDS reads, a dependent tC0
 // table look-up and ~160 VALU instructions per step and wave, i.e. once per line-pair segment of each of the 8 (15) macroblocks of a step
 // AND per lane pair that shares it; here it is done once per macroblock by four threads.
+// Round 8: a phase makes ONE trip to memory -- requests, one wait, results.  The kernel's time is the latency of a workgroup divided by the eight a CU holds, and every
+// wait with a load behind it is a round trip on that chain: the data need two (the records, then the motion they point at), the compiled kernel made up to
+// twenty (profiles/r08_isa_mix.txt; tests/test_dbkp_isa.py holds the property on the assembly).
 // The phases are plain functions of (LDS, frame, first macroblock, thread id); dbkparam2_body at the end is the kernel: tests/emu runs it on the host as it is.
 #ifndef E264_DBKP_H
 #define E264_DBKP_H
@@ -41,7 +44,7 @@ namespace {
 #define DP_RAW 64
 // HAS_L1 = false (round 6): the launcher knows that no packet of the batch predicts from list 1 (every P and I picture: found by the validation that vets a
 // packet anyway) -- the expanded motion has no room for list 1 (80 instead of 144 bytes per record): 18.9 KB of LDS instead of 27.2, EIGHT workgroups per CU
-// instead of six.  This kernel is two dependent trips to memory and three barriers: 0.244 -> 0.192 ms per launch (profiles/r06_ablations.txt item 13).
+// instead of six.  This kernel is dependent trips to memory between barriers (two since round 8, up to twenty before): 0.244 -> 0.192 ms per launch (profiles/r06_ablations.txt item 13).
 template <bool HAS_L1_>
 struct __attribute__((aligned(16))) DbkpLdsT {
 	static constexpr bool HAS_L1 = HAS_L1_;
@@ -81,86 +84,146 @@ E264_DEV int dbkp_addr(const FrameCtx &f, int a0, int j)
 	return min(max(a, 0), n - 1); // clamped: a record that is not a real neighbour is never used (the edge flags gate it)
 }
 
+// Round 8: ONE trip to memory.  Every load of the phase is requested before anything waits for one; no thread runs a load-wait-store body twice, and the
+// one-off duties are spread over the waves: the two record halves that 256 threads leave over go to wave 2, the three tables to wave 1.
 template <class LDS> E264_DEV void dbkp_phase_load(LDS &L, const FrameCtx &f, int a0, int tid)
 {
 	const gu8 *mbs_g = f.mbs_g;
-	for (int i = tid; i < (2 * DP_MBS + 1) * 2; i += DP_NT) { // 32-byte records: 2 pieces of 16 bytes
-		const int j = i >> 1, part = i & 1;
-		*(v4u *)&L.hdr[j][part * 4] = *(const gv4u *)(mbs_g + (size_t)dbkp_addr(f, a0, j) * 32 + part * 16);
-	}
-	if (tid < 52) { L.alpha[tid] = c_alpha[tid]; L.beta[tid] = c_beta[tid]; }
-	if (tid < 52) L.tc3[tid] = (uint32_t)c_tc0[0][tid] << 8 | (uint32_t)c_tc0[1][tid] << 16 | (uint32_t)c_tc0[2][tid] << 24;
-	if (tid == 0) L.any_l1 = 0;
+	constexpr int NH = (2 * DP_MBS + 1) * 2; // 32-byte records: 2 halves of 16 bytes
+	static_assert(NH - DP_NT == 2, "one half per thread and two left over");
+	const bool extra = (uint32_t)(tid - 128) < (uint32_t)(NH - DP_NT), tab = (uint32_t)(tid - 64) < 52u;
+	const int j = tid >> 1, part = tid & 1, k = tab ? tid - 64 : 0;
+	// the requests
+	const v4u r = *(const gv4u *)(mbs_g + (size_t)dbkp_addr(f, a0, j) * 32 + part * 16);
+	v4u r2 = (v4u){any_u32(), any_u32(), any_u32(), any_u32()};
+	if (extra) r2 = *(const gv4u *)(mbs_g + (size_t)dbkp_addr(f, a0, 2 * DP_MBS) * 32 + part * 16);
+	uint32_t ta = any_u32(), tb = any_u32(), t0 = any_u32(), t1 = any_u32(), t2 = any_u32();
+	if (tab) { ta = c_alpha[k]; tb = c_beta[k]; t0 = c_tc0[0][k]; t1 = c_tc0[1][k]; t2 = c_tc0[2][k]; }
+	// their results
+	*(v4u *)&L.hdr[j][part * 4] = r;
+	if (extra) *(v4u *)&L.hdr[2 * DP_MBS][part * 4] = r2;
+	if (tab) { L.alpha[k] = (uint8_t)ta; L.beta[k] = (uint8_t)tb; L.tc3[k] = t0 << 8 | t1 << 16 | t2 << 24; }
+	if (tid == DP_NT - 1) L.any_l1 = 0;
 }
 
 // One list of a macroblock's compact motion record (edge264_cmd.h E264_MOT_*) -> the per-4x4 form the comparisons index:
 // mo[l] = the four quadrants' DPB slots as bytes (0xff: unused), mo[4 + l * 16 + k] = vector of 4x4 block k (unused: 0).
-// Every offset follows from the shape word alone, so the loads do not wait for one another.
-E264_DEV void dbkp_expand_list(const gu8 *motion, uint32_t mot_off, uint32_t h, int l, uint32_t *mo, const bool bottom_row_only = false)
+// Every offset follows from the shape word alone -- a prefix sum over the used quadrants' sizes -- so (round 8) a thread first REQUESTS all it may need
+// (dbkp_fetch_list: loads and nothing else) and then builds references and vectors from registers with selects (dbkp_quad): one trip to memory per thread
+// where the quadrants' conditional loads used to make up to eight, each behind the wait of the one before.
+// What a quadrant asks for, three loads whatever its shape (p: its first dword; s = sub-partition: 0 8x8, 1 8x4, 2 4x8, 3 4x4):
+//   a = dwords p, p + 1            {reference, v0}
+//   b = two dwords at p + (s == 3 ? 2 : s ? 1 : 0)     s 3: {v1, v2}, s 1 / 2: {v0, v1}, s 0: {reference, v0} -- b.y is the quadrant's second vector, or v0 again
+//   c = dword p + (s == 3 ? 4 : 0)                     s 3: v3
+// Every one of them lies inside the quadrant's own 2 / 3 / 5 dwords.  A quadrant the list does not use asks for the first two dwords of the list's part (a used
+// quadrant's, or the uniform form): a list without any part asks for nothing (dbkp_list_has).  So no load leaves the motion section, whatever follows it.
+struct DbkpQuad { v2u a, b; uint32_t c; };
+E264_DEV DbkpQuad dbkp_quad_any() { return (DbkpQuad){(v2u){any_u32(), any_u32()}, (v2u){any_u32(), any_u32()}, any_u32()}; }
+E264_DEV bool dbkp_list_has(uint32_t h, int l) { return (E264_MOT_UNI(h, l) | (h >> (4 * l) & 15u)) != 0; } // the list predicts something of the macroblock
+// byte offset of list l's part in the motion section
+E264_DEV uint32_t dbkp_part_off(uint32_t mot_off, uint32_t h, int l)
 {
-	uint32_t off = mot_off;
-	if (l) { // skip the list-0 part
-		uint32_t n0 = 0;
+	uint32_t n0 = 0;
 #pragma unroll
-		for (int k = 0; k < 4; k++)
-			n0 += E264_MOT_USED(h, k) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, k)) : 0;
-		off += E264_MOT_UNI(h, 0) ? 8 : n0;
-	}
-	const gu32 *rec = (const gu32 *)(motion + off);
-	uint32_t refs = 0xffffffffu;
-	v4u mv[4];
+	for (int k = 0; k < 4; k++)
+		n0 += E264_MOT_USED(h, k) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, k)) : 0;
+	return l ? mot_off + (E264_MOT_UNI(h, 0) ? 8 : n0) : mot_off;
+}
+// the requests of quadrants Q0..3 (Q0 = 2: a top neighbour's bottom row).  Loads only: nothing here uses a loaded value.
+template <int Q0> E264_DEV void dbkp_fetch_list(const gu8 *motion, uint32_t off, uint32_t h, int l, DbkpQuad *F)
+{
+	const bool uni = E264_MOT_UNI(h, l);
+	uint32_t p = 0; // bytes of the used quadrants before q
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		const bool used = !uni && E264_MOT_USED(h, l * 4 + q);
+		const uint32_t sub = used ? E264_MOT_SUB(h, l * 4 + q) : 0;
+		if (q >= Q0) {
+			const uint32_t pa = off + (used ? p : 0);
 #ifdef E264_ABL_DBKP_NOMOT // timing ablation: the motion records are not read (wrong bS): 0.225 -> 0.157 ms, profiles/r03_ablations.txt item 17
-	if (off != 0xfffffffcu && !bottom_row_only) { mo[l] = off; for (int q = 0; q < 4; q++) *(v4u *)&mo[4 + l * 16 + q * 4] = (v4u){off, h, off, h}; return; }
+			F[q - Q0] = (DbkpQuad){(v2u){pa, h}, (v2u){h, pa}, pa};
+#else
+			F[q - Q0].a = *(const gv2u *)(motion + pa);
+			F[q - Q0].b = *(const gv2u *)(motion + (pa + (sub == 3 ? 8u : sub ? 4u : 0u)));
+			F[q - Q0].c = *(const gu32 *)(motion + (pa + (sub == 3 ? 16u : 0u)));
 #endif
-	if (E264_MOT_UNI(h, l)) {
-		const uint32_t r = rec[0], v = rec[1];
-		refs = (r & 255u) * 0x01010101u;
-#pragma unroll
-		for (int q = 0; q < 4; q++) mv[q] = (v4u){v, v, v, v};
-	} else {
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			mv[q] = (v4u){0, 0, 0, 0};
-			if (!E264_MOT_USED(h, l * 4 + q))
-				continue;
-			const uint32_t sub = E264_MOT_SUB(h, l * 4 + q);
-			const uint32_t r = rec[0], v0 = rec[1], v1 = sub ? rec[2] : v0;
-			refs = (refs & ~(255u << (8 * q))) | (r & 255u) << (8 * q);
-			if (sub == 3) mv[q] = (v4u){v0, v1, rec[3], rec[4]};
-			else if (sub == 2) mv[q] = (v4u){v0, v1, v0, v1};
-			else mv[q] = (v4u){v0, v0, v1, v1};
-			rec += 1 + mot_nmv(sub);
 		}
+		p += used ? 4 + 4 * mot_nmv(sub) : 0;
 	}
-	if (bottom_row_only) { // a top neighbour (DbkpLdsT::mot): the two lower quadrants' references, the four vectors of its bottom row
-		((uint16_t *)mo)[l] = (uint16_t)(refs >> 16);
-		mo[1 + l * 4] = mv[2].z; mo[2 + l * 4] = mv[2].w; mo[3 + l * 4] = mv[3].z; mo[4 + l * 4] = mv[3].w;
-		return;
+}
+// quadrant q of list l out of what was fetched for it: its reference byte (0xff: unused) and the vectors of its four 4x4 blocks (unused: 0)
+E264_DEV v4u dbkp_quad(const DbkpQuad &F, uint32_t h, int l, int q, bool has, uint32_t &ref)
+{
+	const bool uni = E264_MOT_UNI(h, l), used = has && (uni || E264_MOT_USED(h, l * 4 + q));
+	const uint32_t sub = uni ? 0 : E264_MOT_SUB(h, l * 4 + q);
+	const uint32_t v0 = F.a.y, v1 = F.b.y;
+	ref = used ? F.a.x & 255u : 255u;
+	const v4u mv = {v0, sub == 3 ? F.b.x : sub == 2 ? v1 : v0, sub == 3 ? v1 : sub == 2 ? v0 : v1, sub == 3 ? F.c : v1}; // 4x4: v0 v1 v2 v3; 4x8: v0 v1 v0 v1; 8x4, 8x8: v0 v0 v1 v1
+	return used ? mv : (v4u){0, 0, 0, 0};
+}
+// full form
+E264_DEV void dbkp_expand_full(const DbkpQuad *F, uint32_t h, int l, bool has, uint32_t *mo)
+{
+	uint32_t refs = 0;
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		uint32_t r;
+		*(v4u *)&mo[4 + l * 16 + q * 4] = dbkp_quad(F[q], h, l, q, has, r);
+		refs |= r << (8 * q);
 	}
 	mo[l] = refs;
-#pragma unroll
-	for (int q = 0; q < 4; q++) *(v4u *)&mo[4 + l * 16 + q * 4] = mv[q];
+}
+// a top neighbour (DbkpLdsT::mot): the two lower quadrants' references, the four vectors of its bottom row.  F: quadrants 2, 3
+E264_DEV void dbkp_expand_bottom(const DbkpQuad *F, uint32_t h, int l, bool has, uint32_t *mo)
+{
+	uint32_t r2, r3;
+	const v4u m2 = dbkp_quad(F[0], h, l, 2, has, r2), m3 = dbkp_quad(F[1], h, l, 3, has, r3);
+	((uint16_t *)mo)[l] = (uint16_t)(r2 | r3 << 8);
+	mo[1 + l * 4] = m2.z; mo[2 + l * 4] = m2.w; mo[3 + l * 4] = m3.z; mo[4 + l * 4] = m3.w;
 }
 
-// after the records have landed: the motion of the inter macroblocks among them (one task per record and list); slice offsets
+// after the records have landed: the motion of the inter macroblocks among them (one task per record and list); slice offsets.
+// No thread expands twice, and nothing a thread requests depends on what it has requested:
+//   <false>  129 tasks (list 0 of every record) on threads 0..128;
+//   <true>   the 130 full-form tasks (left neighbour and own records: record i >> 1, list i & 1) on threads 0..129, the 128 bottom-row tasks (the top neighbours) on
+//            threads 128..255: threads 128 and 129 have one of each and request both before they wait for either.
+// Wave 3 fetches the slices' filter offsets in the same trip.  (The two forms are separate straight-line requests on purpose: where a register is loaded on two
+// paths that join, the join's copy waits for the load.)
 template <class LDS> E264_DEV void dbkp_phase_slices(LDS &L, const FrameCtx &f, int tid)
 {
-	if (f.motion)
-		for (int i = tid; i < (2 * DP_MBS + 1) * 2; i += DP_NT) {
-			const int j = i >> 1, l = i & 1;
-			if ((L.hdr[j][0] & 255) == E264_MB_INTER) {
-				if (!LDS::HAS_L1 && l) // (no room for it and, by the launcher's word, nothing to put there)
-					continue;
-				if (LDS::TOPC && j > DP_MBS) dbkp_expand_list(f.motion, L.hdr[j][5], L.hdr[j][6], l, L.mot[j - DP_MBS - 1], true);
-				else dbkp_expand_list(f.motion, L.hdr[j][5], L.hdr[j][6], l, L.mo[LDS::TOPC && j > DP_MBS ? 0 : j]);
-				const uint32_t h = L.hdr[j][6];
-				if (l && (E264_MOT_UNI(h, 1) || (h >> 4 & 15u))) dbkp_note_l1(&L.any_l1); // (E264_MOT_USED(h, 4..7): the quadrants of list 1)
-			}
-		}
-	if (tid < DP_MBS) {
-		cslice_t s = f.slices + (L.hdr[1 + tid][7] & 0xffff); // E264Mb.dbk_slice
-		L.fo[tid][0] = s->FilterOffsetA; L.fo[tid][1] = s->FilterOffsetB;
+	constexpr bool B = LDS::HAS_L1;
+	constexpr int NFULL = LDS::NFULL; // records in full form
+	const bool motion = f.motion != nullptr;
+	const int l = B ? tid & 1 : 0;
+	const int j = min(B ? tid >> 1 : tid, NFULL - 1);
+	const uint32_t off = L.hdr[j][5], h = L.hdr[j][6];
+	const bool task = motion && tid < (B ? 2 : 1) * NFULL && (L.hdr[j][0] & 255) == E264_MB_INTER; // an inter macroblock's list: its part of LDS is written
+	const bool has = task && dbkp_list_has(h, l);
+	const int t = LDS::TOPC ? max(tid - 2 * DP_MBS, 0) >> 1 : 0, jt = DP_MBS + 1 + t; // top neighbour t
+	const uint32_t offt = L.hdr[jt][5], ht = L.hdr[jt][6];
+	const bool taskt = LDS::TOPC && motion && tid >= 2 * DP_MBS && (L.hdr[jt][0] & 255) == E264_MB_INTER, hast = taskt && dbkp_list_has(ht, l);
+	const bool slice = tid >= DP_NT - DP_MBS;
+	const int si = slice ? tid - (DP_NT - DP_MBS) : 0;
+	// the requests
+	DbkpQuad F[4] = {dbkp_quad_any(), dbkp_quad_any(), dbkp_quad_any(), dbkp_quad_any()}, G[2] = {dbkp_quad_any(), dbkp_quad_any()};
+	if (has) dbkp_fetch_list<0>(f.motion, dbkp_part_off(off, h, l), h, l, F);
+	if (hast) dbkp_fetch_list<2>(f.motion, dbkp_part_off(offt, ht, l), ht, l, G);
+	uint32_t fo = any_u32(); // FilterOffsetA, FilterOffsetB as they lie in the slice (two bytes, one load, nothing done to them before the wait)
+	static_assert(offsetof(E264SliceParams, FilterOffsetB) == offsetof(E264SliceParams, FilterOffsetA) + 1 && !(offsetof(E264SliceParams, FilterOffsetA) & 1), "one 16-bit load");
+	if (slice) {
+		cslice_t s = f.slices + (L.hdr[1 + si][7] & 0xffff); // E264Mb.dbk_slice
+		fo = *(const uint16_t E264_AS_CONST *)&s->FilterOffsetA;
 	}
+	// their results
+	if (task) {
+		dbkp_expand_full(F, h, l, has, L.mo[j]);
+		if (l && has) dbkp_note_l1(&L.any_l1);
+	}
+	if (taskt) {
+		dbkp_expand_bottom(G, ht, l, hast, L.mot[t]);
+		if (l && hast) dbkp_note_l1(&L.any_l1);
+	}
+	if (slice) *(uint16_t *)L.fo[si] = (uint16_t)fo;
 }
 
 // |a - b| of both 16-bit halves at once; A, B: int16 pairs biased by 0x8000 (unsigned order), so the saturating unsigned

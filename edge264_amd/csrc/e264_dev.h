@@ -224,6 +224,13 @@ E264_DEV s16x2 half5p(s16x2 v) // clip255((v + 16) >> 5)
 	const s16x2 s5 = {5, 5}, r16 = {16, 16}, z = {0, 0}, m = {255, 255};
 	return __builtin_elementwise_min(__builtin_elementwise_max((v + r16) >> s5, z), m);
 }
+// A register that holds SOMETHING, at no cost: what a lane does not need is not fetched, but the register still runs through the joins and the
+// arithmetic of the wave, whose results for it are dropped.
+#ifndef E264_HOST_INTRINSICS
+E264_DEV uint32_t any_u32() { uint32_t v; asm("" : "=v"(v)); return v; }
+#else
+E264_DEV uint32_t any_u32() { return 0xa55a5aa5u; } // (host build: something that would show in a result that depended on it)
+#endif
 // One quadrant (list l, 8x8 block q) of a macroblock's compact motion record (edge264_cmd.h): its reference bytes
 // {refPic, refIdx, 0, 0} and the vectors of its four 4x4 blocks (zig order inside the quadrant).  mot_off / mot_hdr: the
 // directory words of E264Mb.modes.  Returns false when the list does not predict the quadrant.

@@ -227,13 +227,8 @@ E264_DEV uint32_t ref_dword(const gu8 *row, int x, int Wb)
 	return v;
 }
 struct Row4 { uint32_t a0, a1, a2, a3; };
-// A register that holds SOMETHING, at no cost: rows a partition does not need are not fetched (the fetch is what this kernel's time
-// is, profiles/r03_ablations.txt item 19) but still run through the arithmetic of the wave, whose results for them are dropped.
-#ifndef E264_HOST_INTRINSICS
-E264_DEV uint32_t any_u32() { uint32_t v; asm("" : "=v"(v)); return v; }
-#else
-E264_DEV uint32_t any_u32() { return 0xa55a5aa5u; } // (host build: something that would show in a result that depended on it)
-#endif
+// any_u32() (e264_dev.h): rows a partition does not need are not fetched (the fetch is what this kernel's time is, profiles/r03_ablations.txt
+// item 19) but still run through the arithmetic of the wave, whose results for them are dropped.
 // NR x 16 bytes around (X, Y): the loads (nothing here uses a loaded value) ...  all: the partition is 8 rows high; else (4 rows)
 // the last four rows of the window are not needed and not fetched
 template <int NR>

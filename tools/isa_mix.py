@@ -14,6 +14,14 @@ which is what a <2 x i16> value costs when the compiler carries it across a join
 name contains "deblock" the loops at depth 2 are listed too: they are the walks of dk_walk_group (e264_kernels.hip), DK_GS unrolled steps each;
 in e264_deblock2* the larger one is the luma walk.
 
+For the kernels whose name contains "dbkparam" the SEGMENTS between the workgroup barriers are listed (key "segments"): a kernel made of phases of loads between
+barriers takes as long as its dependent trips to memory, and a trip is a wait with a load behind it.  Per segment, along the control flow (not the order of the
+text: the compiler lays blocks out as it likes): global loads, `s_waitcnt vmcnt(..)`, and loads_after_wait = the global loads that can execute after a memory
+wait of the same segment that had a global load of the segment to wait for (a loop that holds a load and a wait counts, by its back edge); VALU and the
+registers moved by v_mov_b32 / v_mov_b64.  Only global_load_* count as loads, and a wait counts only from the segment's first global load on: flat loads, and
+waits that come before any global load of the segment, are left out -- in segment 0 that is the prologue's flat load of the destination slot's pointer
+(open_frame) and its wait, a uniform trip of its own in front of the phase ("vm_waits" does include that wait).  Segment 0 is the load phase (with the kernel's prologue), segment 1 the expansion of the motion.
+
 --asm FILE analyses an assembly file that exists already (another tree's, for a side-by-side) instead of compiling this tree.
 """
 import argparse
@@ -76,13 +84,17 @@ def analyse(asm):
         if m:
             cur = {"name": demangle(m.group(1)), "mangled": m.group(1), **new_counts(), "opcodes": collections.Counter(), "loops": collections.OrderedDict()}
             sel_regs, pending, loop, blk_label = set(), {}, None, None
+            body = []
             continue
         if cur is None:
             continue
         if line.startswith(".Lfunc_end"):
+            if "dbkparam" in cur["name"]:
+                cur["segments"] = segments(body)
             kernels[cur["mangled"]] = cur
             cur = None
             continue
+        body.append(line)
         code, _, comment = line.partition(";")
         code = code.strip()
         if re.match(r"\.LBB\d+_\d+:", code) or comment.lstrip().startswith("%bb."):  # a new basic block
@@ -146,6 +158,80 @@ def analyse(asm):
     return kernels
 
 
+def is_vm_wait(op, text):
+    return op == "s_waitcnt" and ("vmcnt" in text or re.fullmatch(r"s_waitcnt\s+(0x[0-9a-fA-F]+|\d+)", text) is not None)
+
+
+def segments(lines):
+    """the inter-barrier segments of one kernel's assembly lines (see the module's text)"""
+    ins, labels = [], {}
+    for line in lines:
+        code = line.partition(";")[0].strip()
+        m = re.match(r"(\.LBB\d+_\d+):", code)
+        if m:
+            labels[m.group(1)] = len(ins)
+            continue
+        if not code or code.startswith(".") or code.endswith(":"):
+            continue
+        parts = code.split(None, 1)
+        ins.append((re.sub(r"_(e32|e64|dpp|sdwa|e64_dpp)$", "", parts[0]), code, [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []))
+    n = len(ins)
+
+    def succ(i):
+        op, _, ops = ins[i]
+        out = []
+        if op.startswith("s_cbranch") or op == "s_branch":
+            if ops and ops[-1] in labels and labels[ops[-1]] < n:
+                out.append(labels[ops[-1]])
+        if op not in ("s_branch", "s_endpgm") and i + 1 < n:
+            out.append(i + 1)
+        return out
+
+    seg = [None] * n  # barriers passed on the way to an instruction
+    work = [0] if n else []
+    if n:
+        seg[0] = 0
+    while work:
+        i = work.pop()
+        for j in succ(i):
+            if seg[j] is None:
+                seg[j] = seg[i] + (ins[i][0] == "s_barrier")
+                work.append(j)
+
+    def flood(starts):
+        """instructions that can execute after one of `starts` without passing a barrier"""
+        seen, work = set(), [i for i in starts if ins[i][0] != "s_barrier"]
+        while work:
+            i = work.pop()
+            for j in succ(i):
+                if j not in seen:
+                    seen.add(j)
+                    if ins[j][0] != "s_barrier":
+                        work.append(j)
+        return seen
+
+    is_load = [op.startswith("global_load_") for op, _, _ in ins]
+    after_load = flood([i for i in range(n) if is_load[i] and seg[i] is not None])
+    waits = [i for i in range(n) if seg[i] is not None and is_vm_wait(ins[i][0], ins[i][1])]
+    after_wait = flood([i for i in waits if i in after_load])
+    out = []
+    for k in range(max([x for x in seg if x is not None], default=-1) + 1):
+        c = {"loads": 0, "vm_waits": 0, "loads_after_wait": 0, "valu": 0, "v_mov": 0, "reg_moves": 0}
+        for i in range(n):
+            if seg[i] != k:
+                continue
+            op, text, ops = ins[i]
+            c["loads"] += is_load[i]
+            c["vm_waits"] += is_vm_wait(op, text)
+            c["loads_after_wait"] += is_load[i] and i in after_wait
+            c["valu"] += op.startswith("v_")
+            if op in ("v_mov_b32", "v_mov_b64"):
+                c["v_mov"] += 1
+                c["reg_moves"] += len(regs(ops[1].split()[0])) if len(ops) > 1 and ops[1].startswith("v") else 0
+        out.append(c)
+    return out
+
+
 def report(kernels, out=sys.stdout):
     for k in kernels.values():
         print(f"{k['name']}", file=out)
@@ -155,6 +241,9 @@ def report(kernels, out=sys.stdout):
             for h, c in k["loops"].items():
                 print(f"   walk loop {h}: VALU {c['valu']}  LDS {c['lds']}  VMEM {c['vmem']}  s_nop {c['s_nop']}  v_mov {c['v_mov']} (registers moved {c['reg_moves']})  "
                       f"identity pairs {c['identity_pairs']}", file=out)
+        for i, c in enumerate(k.get("segments", [])):
+            print(f"   segment {i}: global loads {c['loads']}  s_waitcnt vmcnt {c['vm_waits']}  loads after a wait {c['loads_after_wait']}  |  VALU {c['valu']}  "
+                  f"v_mov {c['v_mov']} (registers moved {c['reg_moves']})", file=out)
         print("   " + "  ".join(f"{op} {n}" for op, n in k["top_opcodes"]), file=out)
 
 
