@@ -117,48 +117,14 @@ template <class LDS> E264_DEV void dbkp_phase_load(LDS &L, const FrameCtx &f, in
 //   c = dword p + (s == 3 ? 4 : 0)                     s 3: v3
 // Every one of them lies inside the quadrant's own 2 / 3 / 5 dwords.  A quadrant the list does not use asks for the first two dwords of the list's part (a used
 // quadrant's, or the uniform form): a list without any part asks for nothing (dbkp_list_has).  So no load leaves the motion section, whatever follows it.
-struct DbkpQuad { v2u a, b; uint32_t c; };
-E264_DEV DbkpQuad dbkp_quad_any() { return (DbkpQuad){(v2u){any_u32(), any_u32()}, (v2u){any_u32(), any_u32()}, any_u32()}; }
-E264_DEV bool dbkp_list_has(uint32_t h, int l) { return (E264_MOT_UNI(h, l) | (h >> (4 * l) & 15u)) != 0; } // the list predicts something of the macroblock
-// byte offset of list l's part in the motion section
-E264_DEV uint32_t dbkp_part_off(uint32_t mot_off, uint32_t h, int l)
-{
-	uint32_t n0 = 0;
-#pragma unroll
-	for (int k = 0; k < 4; k++)
-		n0 += E264_MOT_USED(h, k) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, k)) : 0;
-	return l ? mot_off + (E264_MOT_UNI(h, 0) ? 8 : n0) : mot_off;
-}
-// the requests of quadrants Q0..3 (Q0 = 2: a top neighbour's bottom row).  Loads only: nothing here uses a loaded value.
-template <int Q0> E264_DEV void dbkp_fetch_list(const gu8 *motion, uint32_t off, uint32_t h, int l, DbkpQuad *F)
-{
-	const bool uni = E264_MOT_UNI(h, l);
-	uint32_t p = 0; // bytes of the used quadrants before q
-#pragma unroll
-	for (int q = 0; q < 4; q++) {
-		const bool used = !uni && E264_MOT_USED(h, l * 4 + q);
-		const uint32_t sub = used ? E264_MOT_SUB(h, l * 4 + q) : 0;
-		if (q >= Q0) {
-			const uint32_t pa = off + (used ? p : 0);
-#ifdef E264_ABL_DBKP_NOMOT // timing ablation: the motion records are not read (wrong bS): 0.225 -> 0.157 ms, profiles/r03_ablations.txt item 17
-			F[q - Q0] = (DbkpQuad){(v2u){pa, h}, (v2u){h, pa}, pa};
-#else
-			F[q - Q0].a = *(const gv2u *)(motion + pa);
-			F[q - Q0].b = *(const gv2u *)(motion + (pa + (sub == 3 ? 8u : sub ? 4u : 0u)));
-			F[q - Q0].c = *(const gu32 *)(motion + (pa + (sub == 3 ? 16u : 0u)));
-#endif
-		}
-		p += used ? 4 + 4 * mot_nmv(sub) : 0;
-	}
-}
+// (DbkpQuad, dbkp_list_has, dbkp_part_off and dbkp_fetch_list are in e264_dev.h: the prediction kernel asks the same way.)
 // quadrant q of list l out of what was fetched for it: its reference byte (0xff: unused) and the vectors of its four 4x4 blocks (unused: 0)
 E264_DEV v4u dbkp_quad(const DbkpQuad &F, uint32_t h, int l, int q, bool has, uint32_t &ref)
 {
 	const bool uni = E264_MOT_UNI(h, l), used = has && (uni || E264_MOT_USED(h, l * 4 + q));
 	const uint32_t sub = uni ? 0 : E264_MOT_SUB(h, l * 4 + q);
-	const uint32_t v0 = F.a.y, v1 = F.b.y;
 	ref = used ? F.a.x & 255u : 255u;
-	const v4u mv = {v0, sub == 3 ? F.b.x : sub == 2 ? v1 : v0, sub == 3 ? v1 : sub == 2 ? v0 : v1, sub == 3 ? F.c : v1}; // 4x4: v0 v1 v2 v3; 4x8: v0 v1 v0 v1; 8x4, 8x8: v0 v0 v1 v1
+	const v4u mv = dbkp_quad_vectors(F, sub);
 	return used ? mv : (v4u){0, 0, 0, 0};
 }
 // full form

@@ -233,39 +233,71 @@ E264_DEV uint32_t any_u32() { return 0xa55a5aa5u; } // (host build: something th
 #endif
 // One quadrant (list l, 8x8 block q) of a macroblock's compact motion record (edge264_cmd.h): its reference bytes
 // {refPic, refIdx, 0, 0} and the vectors of its four 4x4 blocks (zig order inside the quadrant).  mot_off / mot_hdr: the
-// directory words of E264Mb.modes.  Returns false when the list does not predict the quadrant.
+// directory words of E264Mb.modes.
 E264_DEV uint32_t mot_nmv(uint32_t sub) { return 0x4221u >> (sub * 4) & 15u; } // vectors of a quadrant: 8x8, 8x4, 4x8, 4x4
-E264_DEV bool mot_quadrant(const gu8 *motion, uint32_t mot_off, uint32_t h, int l, int q, uint32_t &refword, uint32_t mv[4])
+// A list's part of a compact motion record asked for in ONE trip to memory (round 8: the parameter kernel, e264_dbkp.h; round 9: the prediction kernel's
+// classification, e264_pred.h).  Every offset follows from the shape word alone -- a prefix sum over the used quadrants' sizes -- so a thread first REQUESTS
+// all it may need and then builds references and vectors from registers with selects.
+// What a quadrant asks for, three loads whatever its shape (p: its first dword; s = sub-partition: 0 8x8, 1 8x4, 2 4x8, 3 4x4):
+//   a = dwords p, p + 1            {reference, v0}
+//   b = two dwords at p + (s == 3 ? 2 : s ? 1 : 0)     s 3: {v1, v2}, s 1 / 2: {v0, v1}, s 0: {reference, v0} -- b.y is the quadrant's second vector, or v0 again
+//   c = dword p + (s == 3 ? 4 : 0)                     s 3: v3
+// Every one of them lies inside the quadrant's own 2 / 3 / 5 dwords (the uniform form: its 2).
+struct DbkpQuad { v2u a, b; uint32_t c; };
+E264_DEV DbkpQuad dbkp_quad_any() { return (DbkpQuad){(v2u){any_u32(), any_u32()}, (v2u){any_u32(), any_u32()}, any_u32()}; }
+E264_DEV bool dbkp_list_has(uint32_t h, int l) { return (E264_MOT_UNI(h, l) | (h >> (4 * l) & 15u)) != 0; } // the list predicts something of the macroblock
+// byte offset of list l's part in the motion section
+E264_DEV uint32_t dbkp_part_off(uint32_t mot_off, uint32_t h, int l)
 {
-	const bool uni = E264_MOT_UNI(h, l);
-	if (!uni && !E264_MOT_USED(h, l * 4 + q))
-		return false;
-	uint32_t off = mot_off;
-	if (l) { // skip the list-0 part
-		uint32_t n0 = 0;
+	uint32_t n0 = 0;
 #pragma unroll
-		for (int k = 0; k < 4; k++)
-			n0 += E264_MOT_USED(h, k) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, k)) : 0;
-		off += E264_MOT_UNI(h, 0) ? 8 : n0;
-	}
-	const gu32 *rec = (const gu32 *)(motion + off);
-	if (uni) {
-		refword = rec[0];
-		mv[0] = mv[1] = mv[2] = mv[3] = rec[1];
-		return true;
-	}
-	uint32_t skip = 0; // dwords of the used quadrants before q
+	for (int k = 0; k < 4; k++)
+		n0 += E264_MOT_USED(h, k) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, k)) : 0;
+	return l ? mot_off + (E264_MOT_UNI(h, 0) ? 8 : n0) : mot_off;
+}
+// one quadrant's three requests (pa: byte offset of its first dword).  Loads only.
+E264_DEV DbkpQuad dbkp_fetch_quad(const gu8 *motion, uint32_t pa, uint32_t sub)
+{
+	DbkpQuad F;
+	F.a = *(const gv2u *)(motion + pa);
+	F.b = *(const gv2u *)(motion + (pa + (sub == 3 ? 8u : sub ? 4u : 0u)));
+	F.c = *(const gu32 *)(motion + (pa + (sub == 3 ? 16u : 0u)));
+	return F;
+}
+// bytes of list l's used quadrants in front of quadrant q (q may be a lane's own: the prediction kernel has one thread per quadrant)
+E264_DEV uint32_t dbkp_quad_off(uint32_t h, int l, int q)
+{
+	uint32_t p = 0;
 #pragma unroll
 	for (int k = 0; k < 3; k++)
-		if (k < q && E264_MOT_USED(h, l * 4 + k)) skip += 1 + mot_nmv(E264_MOT_SUB(h, l * 4 + k));
-	rec += skip;
-	refword = rec[0];
-	const uint32_t sub = E264_MOT_SUB(h, l * 4 + q);
-	const uint32_t v0 = rec[1], v1 = sub ? rec[2] : v0;
-	if (sub == 3) { mv[0] = v0; mv[1] = v1; mv[2] = rec[3]; mv[3] = rec[4]; }
-	else if (sub == 2) { mv[0] = v0; mv[1] = v1; mv[2] = v0; mv[3] = v1; }
-	else { mv[0] = v0; mv[1] = v0; mv[2] = v1; mv[3] = v1; }
-	return true;
+		p += (k < q && E264_MOT_USED(h, l * 4 + k)) ? 4 + 4 * mot_nmv(E264_MOT_SUB(h, l * 4 + k)) : 0;
+	return p;
+}
+// the vectors of a quadrant's four 4x4 blocks out of what was fetched for it
+E264_DEV v4u dbkp_quad_vectors(const DbkpQuad &F, uint32_t sub)
+{
+	const uint32_t v0 = F.a.y, v1 = F.b.y;
+	return (v4u){v0, sub == 3 ? F.b.x : sub == 2 ? v1 : v0, sub == 3 ? v1 : sub == 2 ? v0 : v1, sub == 3 ? F.c : v1}; // 4x4: v0 v1 v2 v3; 4x8: v0 v1 v0 v1; 8x4, 8x8: v0 v0 v1 v1
+}
+// the requests of quadrants Q0..3 (Q0 = 2: a top neighbour's bottom row).  Loads only: nothing here uses a loaded value.
+template <int Q0> E264_DEV void dbkp_fetch_list(const gu8 *motion, uint32_t off, uint32_t h, int l, DbkpQuad *F)
+{
+	const bool uni = E264_MOT_UNI(h, l);
+	uint32_t p = 0; // bytes of the used quadrants before q
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		const bool used = !uni && E264_MOT_USED(h, l * 4 + q);
+		const uint32_t sub = used ? E264_MOT_SUB(h, l * 4 + q) : 0;
+		if (q >= Q0) {
+			const uint32_t pa = off + (used ? p : 0);
+#ifdef E264_ABL_DBKP_NOMOT // timing ablation: the motion records are not read (wrong bS): 0.225 -> 0.157 ms, profiles/r03_ablations.txt item 17
+			F[q - Q0] = (DbkpQuad){(v2u){pa, h}, (v2u){h, pa}, pa};
+#else
+			F[q - Q0] = dbkp_fetch_quad(motion, pa, sub);
+#endif
+		}
+		p += used ? 4 + 4 * mot_nmv(sub) : 0;
+	}
 }
 
 struct FrameCtx {

@@ -44,6 +44,15 @@ E264_DEV int lds_add(int *p, int v) { return atomicAdd(p, v); }
 E264_DEV void lds_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
 #endif
 
+// any_u32() for registers that are loaded on one side of a join, a definition of its own each (the compiler folds equal any_u32() into one register and then
+// copies it into every register a load may write: sixteen v_mov per item here)
+#ifndef E264_HOST_INTRINSICS
+E264_DEV uint32_t any_own() { uint32_t v; asm volatile("" : "=v"(v)); return v; }
+#else
+E264_DEV uint32_t any_own() { return any_u32(); }
+#endif
+E264_DEV v4u any_v4u() { return (v4u){any_own(), any_own(), any_own(), any_own()}; }
+
 #define PT_W 16                 // tile width in macroblocks (256-byte luma rows, 128-byte chroma rows)
 #ifndef E264_PT_H
 #define E264_PT_H 4             // tile height in macroblocks (build-time: `make variant DEFS=-DE264_PT_H=8` = 512-thread workgroups, 2 per CU)
@@ -83,20 +92,27 @@ struct PredTile { int tx0, ty0; };     // first macroblock of the tile
 // ---------------------------------------------------------------------------------------------------------------------
 // phase 0: headers of the tile, counters
 // ---------------------------------------------------------------------------------------------------------------------
+// Round 9: ONE trip to memory.  The 64 records are 128 16-byte loads, one per thread of the first two waves; the next 32 threads fetch the slot table in the same
+// trip.  Every request goes out before anything waits; the LDS stores come behind the wait.  A record outside the picture is not asked for and reads as zero.
 E264_DEV void pred_phase_setup(PredLds &L, const FrameCtx &f, const PredTile &t, int tid)
 {
+	const bool rec = tid < PT_MBS * 2, tab = (uint32_t)(tid - PT_MBS * 2) < (uint32_t)E264_MAX_SLOTS;
+	const int mb = (tid >> 1) & (PT_MBS - 1), part = tid & 1, k = tab ? tid - PT_MBS * 2 : 0;
+	const int mbx = t.tx0 + (mb & (PT_W - 1)), mby = t.ty0 + mb / PT_W;
+	const bool in = rec && mbx < f.wm && mby < f.hm;
+	// the requests
+	v4u r = (v4u){any_u32(), any_u32(), any_u32(), any_u32()};
+	if (in) r = *(const gv4u *)(f.mbs_g + (size_t)(mby * f.wm + mbx) * 32 + part * 16);
+	v2u d = (v2u){any_u32(), any_u32()};
+	static_assert(sizeof(generic_u8p) == 8, "a slot pointer is one 8-byte load");
+	if (tab) d = *(const gv2u *)((const gu8 *)f.dpb + k * 8);
+	// their results
+	if (rec) *(v4u *)&L.hdr[mb][part * 4] = in ? r : (v4u){0, 0, 0, 0};
+	if (tab) *(v2u *)&L.dpb[k] = d;
 	if (tid < 6) L.cnt[tid] = 0;
 	if (tid < 2) L.rcnt[tid] = 0;
 	if (tid < PT_MBS / 32) L.staged[tid] = 0;
 	if (tid == 0) { L.any_l1 = 0; L.n_inter = 0; L.n_uni = 0; }
-	if (tid < E264_MAX_SLOTS) L.dpb[tid] = f.dpb[tid];
-	const gu32 *mbs_g = (const gu32 *)f.mbs_g;
-	for (int i = tid; i < PT_MBS * 8; i += PT_NT) {
-		const int mb = i >> 3, mbx = t.tx0 + (mb & (PT_W - 1)), mby = t.ty0 + mb / PT_W;
-		uint32_t v = 0;
-		if (mbx < f.wm && mby < f.hm) v = mbs_g[(size_t)(mby * f.wm + mbx) * 8 + (i & 7)];
-		L.hdr[mb][i & 7] = v;
-	}
 }
 
 // The intra bitmap of the tile's rows (e264_kernels.h E264_BITMAP_OFF): one uint16_t per macroblock row of the tile, bit i = macroblock tx0 + i is
@@ -145,30 +161,65 @@ E264_DEV void pred_push(PredLds &L, uint32_t mv, int desc)
 	const int cls = pred_class(mv);
 	*pred_list_slot(L, cls, lds_add(&L.cnt[cls], 1)) = (uint16_t)desc;
 }
+// Round 9: ONE trip to memory.  Where the thread's quadrant lies in its list's part follows from the shape word (dbkp_part_off / dbkp_quad_off, e264_dev.h), so
+// the thread REQUESTS the quadrant's three loads, {reference, v0} of the other list's quadrant where that one is used, and the slice's weighted_bipred_idc --
+// or, in a PCM macroblock, its quadrant's 16 loads --, waits once and builds the words with selects.  Every request lies inside the quadrant's own dwords (or
+// the uniform form's two) of a list that predicts it: nothing leaves the motion section, even where the section ends the packet.  The requests are separate
+// straight-line ones with any_u32() across the joins: a register loaded on two paths that join makes the join's copy wait for the load.
 E264_DEV void pred_phase_classify(PredLds &L, const FrameCtx &f, const PredTile &t, int list, int tid)
 {
 	const int mb = tid >> 2, q = tid & 3;
 	const uint32_t d0 = L.hdr[mb][0];
 	const int kind = (d0 >> 8 & E264_MBF_DONE) ? E264_MB_ABSENT : (int)(d0 & 255); // DONE: written by an earlier packet of the picture, not ours to touch
-	const int mbx = t.tx0 + (mb & (PT_W - 1)), mby = t.ty0 + mb / PT_W;
+	const bool pcm = list == 0 && kind == E264_MB_PCM, inter = kind == E264_MB_INTER && f.motion;
+	const uint32_t mot_off = L.hdr[mb][5], mot_hdr = L.hdr[mb][6]; // E264Mb.modes of an inter macroblock: its motion directory
+	const int lo = list ^ 1;
+	const bool uni = E264_MOT_UNI(mot_hdr, list), unio = E264_MOT_UNI(mot_hdr, lo);
+	const bool used = inter && (uni || E264_MOT_USED(mot_hdr, list * 4 + q));
+	const bool usedo = used && (unio || E264_MOT_USED(mot_hdr, lo * 4 + q)); // refIdx of the other list decides how the two predictions combine
+	const uint32_t sub = uni ? 0 : E264_MOT_SUB(mot_hdr, list * 4 + q);
+	const int qx = q & 1, qy = q >> 1;
+	// the requests
+	DbkpQuad F = dbkp_quad_any();
+	v2u G = (v2u){any_u32(), any_u32()};
+	uint32_t idc = any_u32();
+	if (used) {
+		F = dbkp_fetch_quad(f.motion, dbkp_part_off(mot_off, mot_hdr, list) + (uni ? 0 : dbkp_quad_off(mot_hdr, list, q)), sub);
+		cslice_t s = f.slices + (L.hdr[mb][2] >> 16);
+		idc = *(const uint8_t E264_AS_CONST *)&s->weighted_bipred_idc;
+	}
+	if (usedo) G = *(const gv2u *)(f.motion + (dbkp_part_off(mot_off, mot_hdr, lo) + (unio ? 0 : dbkp_quad_off(mot_hdr, lo, q))));
+	v2u py[8];
+	uint32_t pc[2][4];
+#pragma unroll
+	for (int r = 0; r < 8; r++) { py[r] = (v2u){any_own(), any_own()}; pc[r >> 2][r & 3] = any_own(); }
+	if (pcm) { // edge264_slice.c:914-935: this quadrant's 8x8 luma + 4x4 Cb + 4x4 Cr, all 16 loads before the first store
+		const gu8 *pl = f.payload + L.hdr[mb][4];
+#pragma unroll
+		for (int r = 0; r < 8; r++)
+			py[r] = *(const gv2u *)(pl + (qy * 8 + r) * 16 + qx * 8);
+#pragma unroll
+		for (int p = 0; p < 2; p++)
+#pragma unroll
+			for (int r = 0; r < 4; r++)
+				pc[p][r] = *(const gu32 *)(pl + 256 + p * 64 + (qy * 4 + r) * 8 + qx * 4);
+	}
+	// their results
 	L.refq[tid] = PRED_NO_REF; // until proven otherwise this list does not predict the quadrant (pred_item looks at the neighbour's word)
 	if (list == 0 && (kind == E264_MB_INTER || kind == E264_MB_PCM) && q == 0)
 		lds_or(&L.staged[mb >> 5], 1u << (mb & 31));
-	if (list == 0 && kind == E264_MB_PCM) { // edge264_slice.c:914-935: this quadrant's 8x8 luma + 4x4 Cb + 4x4 Cr
-		const gu8 *pl = f.payload + L.hdr[mb][4];
-		const int qx = q & 1, qy = q >> 1;
-		for (int r = 0; r < 8; r++) {
-			const gu32 *s = (const gu32 *)(pl + (qy * 8 + r) * 16 + qx * 8);
-			uint32_t *d = &L.y[(mb / PT_W) * 16 + qy * 8 + r][(mb & (PT_W - 1)) * 4 + qx * 2];
-			d[0] = s[0]; d[1] = s[1];
-		}
+	if (pcm) {
+#pragma unroll
+		for (int r = 0; r < 8; r++)
+			*(v2u *)&L.y[(mb / PT_W) * 16 + qy * 8 + r][(mb & (PT_W - 1)) * 4 + qx * 2] = py[r];
+#pragma unroll
 		for (int p = 0; p < 2; p++)
+#pragma unroll
 			for (int r = 0; r < 4; r++)
-				L.c[p][(mb / PT_W) * 8 + qy * 4 + r][(mb & (PT_W - 1)) * 2 + qx] = *(const gu32 *)(pl + 256 + p * 64 + (qy * 4 + r) * 8 + qx * 4);
+				L.c[p][(mb / PT_W) * 8 + qy * 4 + r][(mb & (PT_W - 1)) * 2 + qx] = pc[p][r];
 	}
-	if (kind != E264_MB_INTER || !f.motion)
+	if (!inter)
 		return;
-	const uint32_t mot_off = L.hdr[mb][5], mot_hdr = L.hdr[mb][6]; // E264Mb.modes of an inter macroblock: its motion directory
 	if (list == 0 && (E264_MOT_UNI(mot_hdr, 1) || E264_MOT_USED(mot_hdr, 4 + q)))
 		L.any_l1 = 1;
 	if (list == 0 && q == 0) { // what the tile is made of: decides how its chroma is fetched (pred_pair_chroma)
@@ -176,25 +227,22 @@ E264_DEV void pred_phase_classify(PredLds &L, const FrameCtx &f, const PredTile 
 		const bool u0 = E264_MOT_UNI(mot_hdr, 0), u1 = E264_MOT_UNI(mot_hdr, 1), any0 = (mot_hdr & 15u) != 0, any1 = (mot_hdr >> 4 & 15u) != 0;
 		if ((u0 || !any0) && (u1 || !any1) && (u0 || u1)) lds_add(&L.n_uni, 1);
 	}
-	uint32_t refword, mvq[4];
-	if (!mot_quadrant(f.motion, mot_off, mot_hdr, list, q, refword, mvq))
+	if (!used)
 		return;
+	const uint32_t refword = F.a.x;
 	const int pic = (int)(int8_t)refword;
 	if (pic < 0)
 		return;
-	uint32_t otherref = 0xffffffffu, dummy[4]; // refIdx of the other list decides how the two predictions combine
-	if (E264_MOT_UNI(mot_hdr, list ^ 1) || E264_MOT_USED(mot_hdr, (list ^ 1) * 4 + q))
-		mot_quadrant(f.motion, mot_off, mot_hdr, list ^ 1, q, otherref, dummy);
-	const v4u m = {mvq[0], mvq[1], mvq[2], mvq[3]}; // the quadrant's four 4x4 vectors: (0,0) (4,0) (0,4) (4,4)
+	const uint32_t otherref = usedo ? G.x : 0xffffffffu;
+	const v4u m = dbkp_quad_vectors(F, sub); // the quadrant's four 4x4 vectors: (0,0) (4,0) (0,4) (4,4)
 	const int base = tid;
 	// everything the prediction of this quadrant needs goes to LDS here, so that the item phase starts with ONE round
 	// trip to memory (its reference windows) instead of a chain motion -> slot table -> window.
 	// (Tried: entering the quadrants of one 16x16 / 16x8 partition as neighbours of the class list so that their row
 	// fetches share cache lines within an instruction -- no gain, tools/calib/load_rate.hip: the vector memory path takes
 	// 1.5 - 2.5 cycles per lane-row whether the lanes are neighbours or scattered.)
-	cslice_t s = f.slices + (L.hdr[mb][2] >> 16);
 	L.mvq[0][tid] = m.x; L.mvq[1][tid] = m.y; L.mvq[2][tid] = m.z; L.mvq[3][tid] = m.w;
-	L.refq[tid] = (refword & 0xffffu) | (otherref >> 8 & 255u) << 16 | (uint32_t)(uint8_t)s->weighted_bipred_idc << 24;
+	L.refq[tid] = (refword & 0xffffu) | (otherref >> 8 & 255u) << 16 | idc << 24;
 	if (m.x == m.y && m.x == m.z && m.x == m.w) {
 		pred_push(L, m.x, base);
 	} else if (m.x == m.y && m.z == m.w) { // two 8x4
@@ -992,73 +1040,79 @@ E264_DEV uint32_t add_res4(uint32_t px, int r0, int r1, int r2, int r3)
 	return add_res4p(px, r01, r23);
 }
 
-// Levels of a block as packed int16 pairs, whatever the packet stores (int16, or int8 with E264_MBF_LEV8): 8 levels ...
+// Levels of a block as packed int16 pairs, whatever the packet stores (int16, or int8 with E264_MBF_LEV8)
 E264_DEV uint32_t sext2(uint32_t w, int hi) // bytes (2 hi, 2 hi + 1) of w, sign-extended to two int16
 {
 	const uint32_t b0 = hi ? w >> 16 : w;
 	return ((uint32_t)(int)(int8_t)b0 & 0xffffu) | (uint32_t)(int)(int8_t)(b0 >> 8) << 16;
 }
-E264_DEV void levels8(const gu8 *co, int l8, uint32_t cw[4])
-{
-	if (l8) {
-		const v2u v = *(const gv2u *)co;
-		cw[0] = sext2(v.x, 0); cw[1] = sext2(v.x, 1); cw[2] = sext2(v.y, 0); cw[3] = sext2(v.y, 1);
-	} else {
-		const v4u v = *(const gv4u *)co;
-		cw[0] = v.x; cw[1] = v.y; cw[2] = v.z; cw[3] = v.w;
-	}
-}
-// ... and 16
-E264_DEV void levels16(const gu8 *co, int l8, uint32_t cw[8])
-{
-	if (l8) {
-		const v4u v = *(const gv4u *)co;
-		const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-		for (int i = 0; i < 4; i++) { cw[2 * i] = sext2(w[i], 0); cw[2 * i + 1] = sext2(w[i], 1); }
-	} else {
-		const v4u v0 = *(const gv4u *)co, v1 = *(const gv4u *)(co + 16);
-		cw[0] = v0.x; cw[1] = v0.y; cw[2] = v0.z; cw[3] = v0.w; cw[4] = v1.x; cw[5] = v1.y; cw[6] = v1.z; cw[7] = v1.w;
-	}
-}
 
+// Round 9: a residual item makes ONE trip to memory.  res_req4 / res_req8 are an item's requests and nothing else -- the slice's scaling list, the chroma DC
+// words, the levels --, res_item4 / res_item8 take what came back.  A load the macroblock's `coded` bits do not cover is not made: the chroma DC words
+// only where E264_CODED_CHROMA_DC says the payload starts with them, a block's levels only where its bit is set (the second half of a block only in the
+// two-byte form), so nothing is read behind the macroblock's own payload.
+struct ResReq4 { v4u ws, dc, l0, l1; };
 // one 4x4 block (edge264_residual.c:108-187): dequantisation, both butterflies and the add in this lane's registers
-E264_DEV void res_item4(PredLds &L, const FrameCtx &f, int item)
+struct ResGeo4 { int mb, k, pc, l8, qP; uint32_t d0, coded; bool chroma, has_dc, ac; const gu8 *pl, *co; };
+E264_DEV ResGeo4 res_geo4(const PredLds &L, const FrameCtx &f, int item)
 {
-	const int mb = item >> 5, b = item & 31;
-	const uint32_t d0 = L.hdr[mb][0], d1 = L.hdr[mb][1], coded = L.hdr[mb][3];
+	ResGeo4 g;
+	const int b = item & 31;
+	g.mb = item >> 5;
+	const uint32_t d0 = L.hdr[g.mb][0], d1 = L.hdr[g.mb][1], coded = L.hdr[g.mb][3];
 	const bool t8 = (d0 >> 8) & E264_MBF_T8x8;
-	cslice_t s = f.slices + (L.hdr[mb][2] >> 16);
-	const gu8 *pl = f.payload + L.hdr[mb][4];
-	const gi16 *cdc = (const gi16 *)pl;
-	if (coded & E264_CODED_CHROMA_DC) pl += 16;
-	const bool chroma = b >= 16;
-	const int k = b & 15;        // luma block 0..15 / chroma block 0..7
-	const int pc = (k >> 2) & 1; // chroma plane
-	const int l8 = (d0 >> 8 & E264_MBF_LEV8) ? 1 : 0; // one byte per level (edge264_cmd.h): block sizes halve
-	const int lumab = (t8 ? __builtin_popcount(coded & 0x1111) * 128 : __builtin_popcount(coded & 0xffff) * 32) >> l8;
-	const gu8 *co = chroma ? pl + lumab + ((__builtin_popcount((coded >> 16) & ((1u << k) - 1)) * 32) >> l8)
-	                       : pl + ((__builtin_popcount(coded & ((1u << k) - 1)) * 32) >> l8);
-	const int qP = chroma ? (pc ? (int)(d1 & 255) : (int)(d0 >> 24)) : (int)(d0 >> 16 & 255);
-	const int sh = qP / 6, m = qP - sh * 6;
-	const int wl = chroma ? 4 + pc : 3; // weightScale4x4 list of an inter block: Y 3, Cb 4, Cr 5
-	const v4u wsv = *(const gv4u *)((const gu8 *)s + offsetof(E264SliceParams, weightScale4x4) + wl * 16);
-	const uint32_t ws[4] = {wsv.x, wsv.y, wsv.z, wsv.w};
+	g.d0 = d0; g.coded = coded;
+	g.pl = f.payload + L.hdr[g.mb][4];
+	const gu8 *pl = (coded & E264_CODED_CHROMA_DC) ? g.pl + 16 : g.pl;
+	g.chroma = b >= 16;
+	g.k = b & 15;             // luma block 0..15 / chroma block 0..7
+	g.pc = (g.k >> 2) & 1;    // chroma plane
+	g.l8 = (d0 >> 8 & E264_MBF_LEV8) ? 1 : 0; // one byte per level (edge264_cmd.h): block sizes halve
+	const int lumab = (t8 ? __builtin_popcount(coded & 0x1111) * 128 : __builtin_popcount(coded & 0xffff) * 32) >> g.l8;
+	g.co = g.chroma ? pl + lumab + ((__builtin_popcount((coded >> 16) & ((1u << g.k) - 1)) * 32) >> g.l8)
+	                : pl + ((__builtin_popcount(coded & ((1u << g.k) - 1)) * 32) >> g.l8);
+	g.qP = g.chroma ? (g.pc ? (int)(d1 & 255) : (int)(d0 >> 24)) : (int)(d0 >> 16 & 255);
+	g.has_dc = g.chroma && (coded & E264_CODED_CHROMA_DC);
+	g.ac = g.chroma ? (coded >> (16 + g.k) & 1) : true;
+	return g;
+}
+E264_DEV void res_req4(const PredLds &L, const FrameCtx &f, const ResGeo4 &g, ResReq4 &R)
+{
+	cslice_t s = f.slices + (L.hdr[g.mb][2] >> 16);
+	const int wl = g.chroma ? 4 + g.pc : 3; // weightScale4x4 list of an inter block: Y 3, Cb 4, Cr 5
+	R.ws = *(const gv4u *)((const gu8 *)s + offsetof(E264SliceParams, weightScale4x4) + wl * 16);
+	R.dc = any_v4u(); R.l0 = any_v4u(); R.l1 = any_v4u();
+	if (g.has_dc) R.dc = *(const gv4u *)g.pl;             // the eight chroma DC int16: Cb, Cr alternating
+	if (g.ac) R.l0 = *(const gv4u *)g.co;                 // 16 levels in byte form, or the first 8
+	if (g.ac && !g.l8) R.l1 = *(const gv4u *)(g.co + 16);
+}
+// one 4x4 block (edge264_residual.c:108-187): dequantisation, both butterflies and the add in this lane's registers
+E264_DEV void res_item4(PredLds &L, const ResGeo4 &g, const ResReq4 &R)
+{
+	const int mb = g.mb, k = g.k, pc = g.pc;
+	const bool chroma = g.chroma, has_dc = g.has_dc, ac = g.ac;
+	const int sh = g.qP / 6, m = g.qP - sh * 6;
+	const uint32_t ws[4] = {R.ws.x, R.ws.y, R.ws.z, R.ws.w};
 	const int na = na_byte(NA4_0, m), nb = na_byte(NA4_1, m), nc = na_byte(0x171412100e0dull, m);
 	// chroma DC of this block (transform_dc2x2, edge264_residual.c:456-480)
 	int dc = 0;
-	const bool has_dc = chroma && (coded & E264_CODED_CHROMA_DC);
 	if (has_dc) {
-		const int c0 = cdc[pc], c4 = cdc[4 + pc], c2 = cdc[2 + pc], c6 = cdc[6 + pc], n = k & 3;
+		const int hs = pc * 16; // int16 i of the payload's first 16 bytes: half i & 1 of dword i >> 1
+		const int c0 = (int)(int16_t)(R.dc.x >> hs), c2 = (int)(int16_t)(R.dc.y >> hs), c4 = (int)(int16_t)(R.dc.z >> hs), c6 = (int)(int16_t)(R.dc.w >> hs), n = k & 3;
 		const int v = n == 0 ? c0 + c4 + c2 + c6 : n == 1 ? c0 - c4 + c2 - c6 : n == 2 ? c0 + c4 - c2 - c6 : c0 - c4 - c2 + c6;
 		const int LS = (int)((ws[0] & 255u) * (uint32_t)na) << sh;
 		dc = (int)((uint32_t)v * (uint32_t)LS) >> 5;
 	}
-	const bool ac = chroma ? (coded >> (16 + k) & 1) : true;
 	int r[4][4]; // [row][col]
 	if (ac) {
 		uint32_t cw[8];
-		levels16(co, l8, cw);
+		if (g.l8) {
+			const uint32_t w[4] = {R.l0.x, R.l0.y, R.l0.z, R.l0.w};
+#pragma unroll
+			for (int i = 0; i < 4; i++) { cw[2 * i] = sext2(w[i], 0); cw[2 * i + 1] = sext2(w[i], 1); }
+		} else {
+			cw[0] = R.l0.x; cw[1] = R.l0.y; cw[2] = R.l0.z; cw[3] = R.l0.w; cw[4] = R.l1.x; cw[5] = R.l1.y; cw[6] = R.l1.z; cw[7] = R.l1.w;
+		}
 		int tt[4][4]; // [xx][y]
 #pragma unroll
 		for (int y = 0; y < 4; y++) {
@@ -1117,29 +1171,62 @@ E264_DEV void idct8_1dp(s16x2 d[8])
 	d[0] = f0 + f7; d[1] = f2 + f5; d[2] = f4 + f3; d[3] = f6 + f1;
 	d[4] = f6 - f1; d[5] = f4 - f3; d[6] = f2 - f5; d[7] = f0 - f7;
 }
-E264_DEV void res_item8(PredLds &L, const FrameCtx &f, int item)
+struct ResReq8 { v4u ws[4], lv[8]; };
+struct ResGeo8 { int mb, bq, l8, qP; const gu8 *co; };
+E264_DEV ResGeo8 res_geo8(const PredLds &L, const FrameCtx &f, int item)
 {
-	const int mb = item >> 5, bq = (item & 31) - 24;
-	const uint32_t d0 = L.hdr[mb][0], coded = L.hdr[mb][3];
-	cslice_t s = f.slices + (L.hdr[mb][2] >> 16);
-	const gu8 *pl = f.payload + L.hdr[mb][4];
+	ResGeo8 g;
+	g.mb = item >> 5; g.bq = (item & 31) - 24;
+	const uint32_t d0 = L.hdr[g.mb][0], coded = L.hdr[g.mb][3];
+	const gu8 *pl = f.payload + L.hdr[g.mb][4];
 	if (coded & E264_CODED_CHROMA_DC) pl += 16;
-	const int l8 = (d0 >> 8 & E264_MBF_LEV8) ? 1 : 0;
-	const gu8 *co = pl + ((__builtin_popcount(coded & 0x1111 & ((1u << (bq * 4)) - 1)) * 128) >> l8);
+	g.l8 = (d0 >> 8 & E264_MBF_LEV8) ? 1 : 0;
+	g.co = pl + ((__builtin_popcount(coded & 0x1111 & ((1u << (g.bq * 4)) - 1)) * 128) >> g.l8);
+	g.qP = (int)(d0 >> 16 & 255);
+	return g;
+}
+E264_DEV void res_req8(const PredLds &L, const FrameCtx &f, const ResGeo8 &g, ResReq8 &R)
+{
+	cslice_t s = f.slices + (L.hdr[g.mb][2] >> 16);
 	const gu8 *wsp = (const gu8 *)s + offsetof(E264SliceParams, weightScale8x8) + 64; // list 1: inter Y
-	const int qP = (int)(d0 >> 16 & 255), div = qP / 6, m = qP - div * 6;
+#pragma unroll
+	for (int i = 0; i < 4; i++) {
+		R.ws[i] = *(const gv4u *)(wsp + i * 16);
+		R.lv[i] = *(const gv4u *)(g.co + i * 16); // 64 levels in byte form, or the first 32
+		R.lv[4 + i] = any_v4u();
+	}
+	if (!g.l8) {
+#pragma unroll
+		for (int i = 0; i < 4; i++) R.lv[4 + i] = *(const gv4u *)(g.co + 64 + i * 16);
+	}
+}
+E264_DEV void res_item8(PredLds &L, const ResGeo8 &g, const ResReq8 &R)
+{
+	const int mb = g.mb, bq = g.bq;
+	const int qP = g.qP, div = qP / 6, m = qP - div * 6;
 	// residual.c:214-247 has two forms (qP < 36: saturate((level * LS + 2^(5 - div)) >> (6 - div)); else level * int16(LS << (div - 6)), wrapped): one
 	// flow for both -- qP is per lane here, a two-way form is a divergent branch around every one of the 64 coefficients
 	const int shl = max(div - 6, 0), shr = max(6 - div, 0), rnd = div < 6 ? 1 << (5 - div) : 0;
 	const int lo = div < 6 ? -32768 : (int)0x80000000, hi = div < 6 ? 32767 : 0x7fffffff;
+	uint32_t lev8[8][4]; // row i of the block as four int16 pairs
+	if (g.l8) {
+#pragma unroll
+		for (int i = 0; i < 8; i++) {
+			const v4u v = R.lv[i >> 1];
+			const uint32_t a = (i & 1) ? v.z : v.x, b = (i & 1) ? v.w : v.y;
+			lev8[i][0] = sext2(a, 0); lev8[i][1] = sext2(a, 1); lev8[i][2] = sext2(b, 0); lev8[i][3] = sext2(b, 1);
+		}
+	} else {
+#pragma unroll
+		for (int i = 0; i < 8; i++) { lev8[i][0] = R.lv[i].x; lev8[i][1] = R.lv[i].y; lev8[i][2] = R.lv[i].z; lev8[i][3] = R.lv[i].w; }
+	}
 	// pass 1 (residual.c:250-296): for every j, the 1-D transform over i of d[i][j] = level c[i*8+j] dequantised; packed pairs (j, j+1)
 	s16x2 t[8][4]; // [i][pair of j]
 #pragma unroll
 	for (int i = 0; i < 8; i++) {
-		uint32_t cw[4];
-		levels8(co + ((i * 16) >> l8), l8, cw);
-		const v2u wv = *(const gv2u *)(wsp + i * 8);
-		const uint32_t ww[2] = {wv.x, wv.y};
+		const uint32_t *cw = lev8[i];
+		const v4u wv = R.ws[i >> 1];
+		const uint32_t ww[2] = {(i & 1) ? wv.z : wv.x, (i & 1) ? wv.w : wv.y};
 #pragma unroll
 		for (int jp = 0; jp < 4; jp++) {
 			int dq[2];
@@ -1194,21 +1281,48 @@ E264_DEV void res_item8(PredLds &L, const FrameCtx &f, int item)
 		}
 	}
 }
+// Thread tid takes 4x4 item tid and 8x8 item PT_NT - 1 - tid.  The 8x8 blocks go to the workgroup's LAST threads: the 4x4
+// list rarely fills all four waves, so the long 8x8 transforms run beside the 4x4 ones instead of behind them on the first wave (the others wait at the
+// barrier for the slowest: 20 % of the kernel's wave time).  A thread that has one item of each requests both before it waits for either.
 E264_DEV void pred_phase_residual(PredLds &L, const FrameCtx &f, int tid)
 {
 	const int n4 = L.rcnt[0], n8 = L.rcnt[1];
 	const uint16_t *l4 = &L.lst[0][0], *l8 = &L.lst[2][0];
-	for (int p = tid; p < n4; p += PT_NT)
-		res_item4(L, f, l4[p]);
 #ifdef E264_PRED_RES8_FIRST_WAVES
-	for (int p = tid; p < n8; p += PT_NT)
-		res_item8(L, f, l8[p]);
+	const int p8 = tid;
 #else
-	// the 8x8 blocks from the workgroup's LAST threads: the 4x4 list rarely fills all four waves, so the long 8x8 transforms run beside
-	// the 4x4 ones instead of behind them on the first wave (the others wait at the barrier for the slowest: 20 % of the kernel's wave time)
-	for (int p = PT_NT - 1 - tid; p < n8; p += PT_NT)
-		res_item8(L, f, l8[p]);
+	const int p8 = PT_NT - 1 - tid;
 #endif
+	const bool has4 = tid < n4, has8 = p8 < n8;
+	const ResGeo4 g4 = res_geo4(L, f, has4 ? l4[tid] : 0);
+	const ResGeo8 g8 = res_geo8(L, f, has8 ? l8[p8] : 24);
+	// the requests
+	ResReq4 R4 = {any_v4u(), any_v4u(), any_v4u(), any_v4u()};
+	ResReq8 R8;
+#pragma unroll
+	for (int i = 0; i < 8; i++) { R8.ws[i >> 1] = any_v4u(); R8.lv[i] = any_v4u(); }
+	if (has4) res_req4(L, f, g4, R4);
+	if (has8) res_req8(L, f, g8, R8);
+	// their results
+	if (has4) res_item4(L, g4, R4);
+	if (has8) res_item8(L, g8, R8);
+}
+// a tile with more 4x4 blocks than threads (there are never more 8x8 blocks: four per macroblock): pass k >= 1, thread tid takes item k * PT_NT + tid
+static_assert(PT_MBS * 4 <= PT_NT, "the 8x8 blocks of a tile are one pass");
+E264_DEV void pred_phase_residual_more(PredLds &L, const FrameCtx &f, int k, int tid)
+{
+	const int p = k * PT_NT + tid;
+	if (p >= L.rcnt[0])
+		return;
+	const uint16_t *l4 = &L.lst[0][0]; // (the 4x4 list runs through lst[0] and lst[1])
+	const ResGeo4 g4 = res_geo4(L, f, l4[p]);
+	ResReq4 R4;
+	res_req4(L, f, g4, R4);
+	res_item4(L, g4, R4);
+}
+E264_DEV int pred_residual_passes(const PredLds &L)
+{
+	return (L.rcnt[0] + PT_NT - 1) / PT_NT;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1278,6 +1392,11 @@ E264_DEV void pred_kernel_body(PredLds &L, const E264Job &job, const int bx, con
 	E264_WG_SYNC();
 	PH(8);
 	pred_phase_residual(L, f, tid);
+	// a pass is one trip to memory, and passes are phases of their own (a tile with more than PT_NT 4x4 blocks: uniform over the workgroup)
+	for (int k = 1, n = pred_residual_passes(L); k < n; k++) {
+		E264_WG_SYNC();
+		pred_phase_residual_more(L, f, k, tid);
+	}
 	PH(9);
 	E264_WG_SYNC();
 	PH(10);

@@ -22,6 +22,10 @@ registers moved by v_mov_b32 / v_mov_b64.  Only global_load_* count as loads, an
 waits that come before any global load of the segment, are left out -- in segment 0 that is the prologue's flat load of the destination slot's pointer
 (open_frame) and its wait, a uniform trip of its own in front of the phase ("vm_waits" does include that wait).  Segment 0 is the load phase (with the kernel's prologue), segment 1 the expansion of the motion.
 
+For the kernels whose name contains "e264_pred" the segments are listed with the same fields, cut differently: that kernel's barriers are not all on one path (its
+list-1 phases are behind a branch), so segment 0 is what runs from the entry to a first barrier and segment k what runs from the k-th s_barrier of the text to a
+next one; what two barriers lead to is counted in both (tests/test_pred_isa.py tells the phases apart by their loads; profiles/r09_isa_mix.txt names them).
+
 --asm FILE analyses an assembly file that exists already (another tree's, for a side-by-side) instead of compiling this tree.
 """
 import argparse
@@ -91,6 +95,8 @@ def analyse(asm):
         if line.startswith(".Lfunc_end"):
             if "dbkparam" in cur["name"]:
                 cur["segments"] = segments(body)
+            elif "e264_pred" in cur["name"]:
+                cur["segments"] = segments(body, by_barrier=True)
             kernels[cur["mangled"]] = cur
             cur = None
             continue
@@ -162,8 +168,10 @@ def is_vm_wait(op, text):
     return op == "s_waitcnt" and ("vmcnt" in text or re.fullmatch(r"s_waitcnt\s+(0x[0-9a-fA-F]+|\d+)", text) is not None)
 
 
-def segments(lines):
-    """the inter-barrier segments of one kernel's assembly lines (see the module's text)"""
+def segments(lines, by_barrier=False):
+    """the inter-barrier segments of one kernel's assembly lines (see the module's text).  by_barrier: a kernel whose barriers are not all on one path
+    (e264_pred_kernel: its list-1 phases): segment 0 is what runs from the entry to a first barrier, segment k what runs from the k-th s_barrier of the text
+    to a next one; what two barriers lead to (the residual lists behind either list's items) is counted in both"""
     ins, labels = [], {}
     for line in lines:
         code = line.partition(";")[0].strip()
@@ -215,11 +223,14 @@ def segments(lines):
     waits = [i for i in range(n) if seg[i] is not None and is_vm_wait(ins[i][0], ins[i][1])]
     after_wait = flood([i for i in waits if i in after_load])
     out = []
-    for k in range(max([x for x in seg if x is not None], default=-1) + 1):
+    if by_barrier:
+        bars = [i for i in range(n) if ins[i][0] == "s_barrier" and seg[i] is not None]
+        members = [flood([0]) | {0}] + [flood(succ(b)) | set(succ(b)) for b in bars] if n else []
+    else:
+        members = [{i for i in range(n) if seg[i] == k} for k in range(max([x for x in seg if x is not None], default=-1) + 1)]
+    for member in members:
         c = {"loads": 0, "vm_waits": 0, "loads_after_wait": 0, "valu": 0, "v_mov": 0, "reg_moves": 0}
-        for i in range(n):
-            if seg[i] != k:
-                continue
+        for i in sorted(member):
             op, text, ops = ins[i]
             c["loads"] += is_load[i]
             c["vm_waits"] += is_vm_wait(op, text)
