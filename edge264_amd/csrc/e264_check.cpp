@@ -17,10 +17,10 @@ API const char *e264hip_last_error(void) { return e264_err; }
 int e264_check_header(const void *packet, size_t bytes, E264PacketInfo *info)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
-	if (!packet || bytes < sizeof(*h) || h->magic != E264_MAGIC || (h->version != E264_VERSION && h->version != E264_VERSION_COMPACT) || h->total_bytes > bytes)
+	if (!packet || bytes < sizeof(*h) || h->magic != E264_MAGIC || (h->version != E264_VERSION && !e264_wire_level(h->version)) || h->total_bytes > bytes)
 		return fail(EINVAL, "not a command packet");
 	if (h->dst_slot < 0 || h->dst_slot >= E264_MAX_SLOTS) return fail(EINVAL, "dst_slot");
-	if (h->version == E264_VERSION_COMPACT) {
+	if (e264_wire_level(h->version)) {
 		if (e264_check_compact(packet, h->total_bytes)) return fail(EINVAL, "wire packet structure");
 	} else {
 		size_t n_mb = (size_t)h->width_mbs * h->height_mbs;
@@ -28,7 +28,7 @@ int e264_check_header(const void *packet, size_t bytes, E264PacketInfo *info)
 		if (h->motion_off && (h->motion_off < need || (need = (size_t)h->motion_off) > h->total_bytes)) return fail(EINVAL, "motion section");
 		if (need > h->payload_off || (size_t)h->payload_off + h->payload_bytes > h->total_bytes) return fail(EINVAL, "packet layout");
 	}
-	*info = {h->dst_slot, h->width_mbs, h->height_mbs, h->version == E264_VERSION_COMPACT ? e264_expand_area_bytes(packet) : 0,
+	*info = {h->dst_slot, h->width_mbs, h->height_mbs, e264_wire_level(h->version) ? e264_expand_area_bytes(packet) : 0,
 		(uint64_t)h->plane_size_Y + h->plane_size_C, h->ref_slots, true, true};
 	return 0;
 }
@@ -114,9 +114,11 @@ int e264_check_records(const void *packet, E264SlotView slots, E264PacketInfo *i
 	if (slots.ptr && slots.bytes && slots.ptr[info->dst_slot] && w.frame_need > slots.bytes[info->dst_slot]) return fail(EINVAL, "picture larger than the destination slot");
 	const uint8_t *mot = h->motion_off ? p + h->motion_off : nullptr; // compact motion records, up to payload_off
 	const uint32_t mot_bytes = h->motion_off ? h->payload_off - h->motion_off : 0;
-	if (h->version == E264_VERSION_COMPACT) {
+	if (e264_wire_level(h->version)) {
 		// A wire packet (include/edge264_compact.h; e264_check_header has vetted its structure) means what its expansion means: every entry is held
 		// against the same checks as the version-4 record e264_expand_kernel will make of it -- walked in place, entry by entry, without unfolding the packet.
+		// Version 6 is held to the canonical form as well (spare bits zero, a tail only where it says something): folding its expansion again gives its own bytes.
+		const bool v6 = h->version == E264_VERSION_COMPACT2;
 		E264CompactCursor c;
 		e264_cursor_init(&c, p);
 		for (int a = 0, r, n_mbs = info->n_mbs(), col = 0; a < n_mbs; a++, col = col + 1 == h->width_mbs ? 0 : col + 1) {
@@ -125,7 +127,8 @@ int e264_check_records(const void *packet, E264SlotView slots, E264PacketInfo *i
 			E264Mb m;
 			uint8_t rec[16];
 			if (!cls) { memcpy(&m, e, 32); r = check_mb(w, m, a, col, mot, mot_bytes); }
-			else r = check_mb(w, m, a, col, rec, e264_compact_entry_expand(e, cls == 2, 0, &m, rec));
+			else if (v6 && !e264_compact_entry_canonical(e, cls)) r = fail(EINVAL, "wire entry not in canonical form");
+			else r = check_mb(w, m, a, col, rec, e264_compact_entry_expand(e, cls, 0, &m, rec));
 			if (r) return r;
 		}
 	} else {
@@ -199,26 +202,30 @@ API int e264hip_packet_check(const void *packet, size_t bytes)
 }
 
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.
-API size_t e264hip_packet_compact_bound(const void *packet, size_t bytes)
+API size_t e264hip_packet_compact2_bound(const void *packet, size_t bytes, int level)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
-	return (packet && bytes >= sizeof(*h) && h->magic == E264_MAGIC && h->version == E264_VERSION) ? e264_compact_bound(packet) : 0;
+	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
+	return (packet && bytes >= sizeof(*h) && h->magic == E264_MAGIC && h->version == E264_VERSION) ? e264_compact_bound(packet, level) : 0;
 }
-// version 4 -> version 5; the input must pass e264hip_packet_check (checked here).  Returns the size written, 0 on error (e264hip_last_error).
-API size_t e264hip_packet_compact(const void *packet, size_t bytes, void *out, size_t cap)
+API size_t e264hip_packet_compact_bound(const void *packet, size_t bytes) { return e264hip_packet_compact2_bound(packet, bytes, 1); }
+// version 4 -> version 5 (level 1) or 6 (level 2); the input must pass e264hip_packet_check (checked here).  Returns the size written, 0 on error (e264hip_last_error).
+API size_t e264hip_packet_compact2(const void *packet, size_t bytes, int level, void *out, size_t cap)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
+	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
 	if (!packet || !out || bytes < sizeof(*h) || h->version != E264_VERSION || e264hip_packet_check(packet, bytes)) { fail(EINVAL, "packet_compact: not a sound version-4 packet"); return 0; }
-	const size_t r = e264_compact_packet(packet, h->total_bytes, out, cap);
+	const size_t r = e264_compact_packet(packet, h->total_bytes, level, out, cap);
 	if (!r) fail(EINVAL, "packet_compact: output buffer too small");
 	return r;
 }
-// version 5 -> the canonical version-4 packet.  out == NULL: the size needed.  0 on error.
+API size_t e264hip_packet_compact(const void *packet, size_t bytes, void *out, size_t cap) { return e264hip_packet_compact2(packet, bytes, 1, out, cap); }
+// version 5 or 6 -> the canonical version-4 packet.  out == NULL: the size needed.  0 on error.
 API size_t e264hip_packet_expand(const void *packet, size_t bytes, void *out, size_t cap)
 {
 	E264PacketInfo info;
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
-	if (e264_check_header(packet, bytes, &info) || h->version != E264_VERSION_COMPACT) { fail(EINVAL, "packet_expand: not a sound wire packet"); return 0; }
+	if (e264_check_header(packet, bytes, &info) || !e264_wire_level(h->version)) { fail(EINVAL, "packet_expand: not a sound wire packet"); return 0; }
 	if (!out) return e264_expanded_bytes(packet);
 	const size_t r = e264_expand_packet(packet, h->total_bytes, out, cap);
 	if (!r) fail(EINVAL, "packet_expand: output buffer too small");

@@ -47,13 +47,21 @@ def load():
     return L
 
 
-def capture_packets(stream: bytes, n_threads: int = 0, compact: bool = False) -> tuple[list[bytes], int, float]:
+def _level(compact) -> int:
+    """`compact` of the functions below as the level e264front_set_compact takes: 0 off, 1 version 5, 2 version 6"""
+    level = int(compact)
+    if level not in (0, 1, 2):
+        raise FrontError(f"compact={compact!r}: 0, 1 or 2")
+    return level
+
+
+def capture_packets(stream: bytes, n_threads: int = 0, compact: bool | int = False) -> tuple[list[bytes], int, float]:
     """Parses `stream` (Annex B) with the capture sink.  Returns (command packets in decoding order, output frames the
     decoder handed out, seconds of host time spent parsing + emitting).  compact: pictures with inter macroblocks come in the
-    wire form (version 5, include/edge264_compact.h)."""
+    wire form (include/edge264_compact.h): True or 1 gives version 5, 2 gives version 6."""
     L = load()
     L.e264front_set_sink(1)
-    L.e264front_set_compact(1 if compact else 0)
+    L.e264front_set_compact(_level(compact))
     buf = C.create_string_buffer(stream + b"\0" * 64, len(stream) + 64)
     base = C.addressof(buf)
     end = base + len(stream)
@@ -95,13 +103,13 @@ def capture_packets(stream: bytes, n_threads: int = 0, compact: bool = False) ->
     return packets, frames, spent
 
 
-def decode_timed(stream: bytes, sink: int = 0, compact: bool = False) -> dict:
+def decode_timed(stream: bytes, sink: int = 0, compact: bool | int = False) -> dict:
     """ONE decoder through the edge264.h API on the device sink (edge264_decode_NAL / edge264_get_frame, frames downloaded to the host mirror as an
     application sees them): wall time per output picture.  bench.py's single-stream latency leg -- the figure the reference's own `edge264_test -b`
     prints for itself (/root/reference/src/edge264_test.c:522-542), per picture."""
     L = load()
     L.e264front_set_sink(sink)
-    L.e264front_set_compact(1 if compact else 0)
+    L.e264front_set_compact(_level(compact))
     buf = C.create_string_buffer(stream + b"\0" * 64, len(stream) + 64)
     base = C.addressof(buf)
     end = base + len(stream)

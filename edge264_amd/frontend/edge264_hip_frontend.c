@@ -129,9 +129,10 @@ PUBLIC void e264front_set_device(int ordinal) { g_device_ordinal = ordinal; }
 PUBLIC void e264front_set_download(int on) { g_download = on; }
 PUBLIC void e264front_set_pinned(int on) { g_pkt_pinned = on; }
 /* 1: pictures with inter macroblocks leave in the WIRE form (version 5, include/edge264_compact.h: P_Skip / plain 16x16 macroblocks without residual in 12
- * bytes instead of 40), which the back end unfolds on the device; decoders allocated afterwards.  Also E264_FRONT_COMPACT=1 in the environment. */
+ * bytes instead of 40), which the back end unfolds on the device; 2: in its second level (version 6: the plain 16x16 macroblocks WITH residual in 24 bytes
+ * too); any other value but 0 counts as 1.  Decoders allocated afterwards.  Also E264_FRONT_COMPACT=1 / =2 in the environment. */
 static int g_compact = -1;
-PUBLIC void e264front_set_compact(int on) { g_compact = on != 0; }
+PUBLIC void e264front_set_compact(int on) { g_compact = on == 2 ? 2 : on != 0; }
 
 /* the device object of GPU `ordinal` (opened on first use); a decoder is bound to the GPU selected by e264front_set_device at
  * the time of its edge264_alloc -- several GPUs in one process: one decoder population per GPU, SURVEY.md 8(e) */
@@ -402,7 +403,7 @@ static int e264_finish_frame_(E264Emitter *e, int slot, int partial)
 	 * bytes to write, and over PCIe, for an encoder's pictures); a picture that goes out in several packets edits its records in a version-4 packet first
 	 * (a buffer of the emitter's), which is then folded; pictures without inter macroblocks have nothing to fold and leave as version 4 */
 	const int fold = e->compact && n_inter > 0;
-	const size_t out_cap = fold ? total + e264_compact_table_bytes((uint32_t)b->width_mbs, (uint32_t)b->height_mbs) + 64 : total;
+	const size_t out_cap = fold ? total + e264_compact_table_bytes((uint32_t)b->width_mbs, (uint32_t)b->height_mbs, e->compact) + 64 : total;
 	uint8_t *out;
 	if (e->sink_kind == 0) out = hip.packet_buffer(e->hip_stream, out_cap);
 	else out = e264_pkt_alloc_on(out_cap, ON_DEVICE(e) ? (E264Device *)e->hip_dev : NULL);
@@ -437,7 +438,7 @@ static int e264_finish_frame_(E264Emitter *e, int slot, int partial)
 	 * (Until round 4 the whole 0.4 MB in front of the payload was cleared first and then overwritten.) */
 	if (fold_direct) {
 		h.total_bytes = (uint32_t)total; /* (of the version-4 form: the bound the fold checks its room against) */
-		total = e264_compact_sections(&h, b->slices, b->mbs, b->mot, b->payload, b->payload_len, out, out_cap); /* (never 0: out_cap is its bound) */
+		total = e264_compact_sections(&h, b->slices, b->mbs, b->mot, b->payload, b->payload_len, e->compact, out, out_cap); /* (never 0: out_cap is its bound) */
 		b->active = 0;
 		goto send;
 	}
@@ -475,7 +476,7 @@ static int e264_finish_frame_(E264Emitter *e, int slot, int partial)
 	if (!partial)
 		b->active = 0;
 	if (fold)
-		total = e264_compact_packet(pkt, total, out, out_cap);
+		total = e264_compact_packet(pkt, total, e->compact, out, out_cap);
 send:
 	pkt = out;
 	if (e->sink_kind == 0)
@@ -535,7 +536,8 @@ PUBLIC Edge264Decoder *edge264_alloc(int n_threads, Edge264LogCb log_cb, void *l
 	if (!e)
 		return NULL;
 	e->sink_kind = g_sink_kind;
-	e->compact = g_compact >= 0 ? g_compact : (getenv("E264_FRONT_COMPACT") && atoi(getenv("E264_FRONT_COMPACT")) != 0);
+	const int env_compact = getenv("E264_FRONT_COMPACT") ? atoi(getenv("E264_FRONT_COMPACT")) : 0;
+	e->compact = g_compact >= 0 ? g_compact : env_compact == 2 ? 2 : env_compact != 0;
 	e->user_alloc = alloc_cb; e->user_free = free_cb; e->user_arg = alloc_arg;
 	e->flush_partial = e264_flush_partial;
 	if (ON_DEVICE(e)) {

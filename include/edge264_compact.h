@@ -1,4 +1,4 @@
-/* edge264_compact.h -- the WIRE form of a command packet (version 5): the same information as version 4 (edge264_cmd.h) in fewer bytes for the link.
+/* edge264_compact.h -- the WIRE form of a command packet (versions 5 and 6): the same information as version 4 (edge264_cmd.h) in fewer bytes for the link.
  *
  * Why.  A packet crosses PCIe once and is then read by four kernels; with the copy inside the clock the back end runs at 0.9 of the link
  * (bench.py pcie_inclusive.link_frac), and most macroblocks of an encoder-made stream say "one vector per list, no residual" -- P_Skip, B_Skip / Direct with one
@@ -25,6 +25,13 @@
  *                               counts in THIS packet's motion section)
  *   motion_off -> the motion records of the FULL inter macroblocks only      payload_off -> as in version 4
  *
+ * Version 6 (level 2 of the fold; opt-in, version 5 stays what it is) also folds the inter macroblock of one partition per list WITH residual: the entry above
+ * followed by a 12-byte tail E264MbCompactTail {coded, payload_off, nz_mask}, 24 bytes for one list and 32 for both (no gain in the table, but 16 bytes fewer
+ * in the motion section), and its flags may carry E264_MBF_T8x8 and E264_MBF_LEV8.  The header grows to 24 bytes (n_resid) and a third bitmap follows bbits:
+ *               uint32_t rbits[height_mbs][words_per_row]    ... and carries the residual tail (a subset of cbits)
+ * An entry lies at row_off[y] + 32 x - 20 c + 8 b + 12 r (compact, two-list and residual macroblocks before it in the row: three popcounts); its motion
+ * record's place depends on c and b alone, so the directory is the same.  The expansion is the same kind of thing: a canonical version-4 packet.
+ *
  * Plain C99, no dependencies: the front end (C), the back end (C++) and, through the back end's exports, the Python tools share this one definition. */
 #ifndef EDGE264_COMPACT_H
 #define EDGE264_COMPACT_H
@@ -35,19 +42,29 @@
 extern "C" {
 #endif
 
-#define E264_VERSION_COMPACT 5u
+#define E264_VERSION_COMPACT 5u  /* level 1 of the fold */
+#define E264_VERSION_COMPACT2 6u /* level 2: ... and the one-partition macroblocks with residual */
+/* level of the fold a packet of this version is in: 0 none (not a wire packet), 1, 2 */
+static inline int e264_wire_level(uint32_t version) { return version == E264_VERSION_COMPACT ? 1 : version == E264_VERSION_COMPACT2 ? 2 : 0; }
 /* mot_hdr of "one partition per list": the list's four quadrant bits + its uniform bit (edge264_cmd.h E264_MOT_*) */
 #define E264_MOT_HDR_UNI0 0x10fu
 #define E264_MOT_HDR_UNI1 0x2f0u
 #define E264_MOT_HDR_UNI01 0x3ffu
 #define E264_MBCF_LIST1 0x80u /* E264MbCompact.flags: the (single) list is list 1 */
 
-typedef struct E264CompactHdr { /* 16 bytes at mbs_off of a version-5 packet */
+typedef struct E264CompactHdr { /* at mbs_off of a wire packet: these 16 bytes in version 5, 24 in version 6 (E264CompactHdr2) */
 	uint32_t n_compact;      /* compact macroblocks, the two-list ones included */
 	uint32_t n_both;         /* ... of which predict from both lists */
 	uint32_t entries_bytes;  /* 32 * n_mbs - 20 * n_compact + 8 * n_both */
 	uint32_t words_per_row;  /* (width_mbs + 31) / 32 */
 } E264CompactHdr;
+typedef struct E264CompactHdr2 { /* 24 bytes at mbs_off of a version-6 packet */
+	uint32_t n_compact, n_both;
+	uint32_t entries_bytes;  /* 32 * n_mbs - 20 * n_compact + 8 * n_both + 12 * n_resid */
+	uint32_t words_per_row;
+	uint32_t n_resid;        /* compact macroblocks that carry the residual tail */
+	uint32_t zero;
+} E264CompactHdr2;
 
 typedef struct E264MbCompact { /* 12 bytes: an inter macroblock of ONE partition without residual */
 	uint8_t flags;       /* E264Mb.flags: EDGE_LEFT, EDGE_TOP, DEBLOCK (a macroblock with any other flag keeps its full record) | E264_MBCF_LIST1 */
@@ -62,51 +79,74 @@ typedef struct E264MbCompactL1 { /* 8 bytes behind the E264MbCompact of a two-li
 	uint8_t ref_slot, ref_idx, zero[2];
 	int16_t mv[2];
 } E264MbCompactL1;
+typedef struct E264MbCompactTail { /* 12 bytes at the end of a residual entry (version 6): the three fields of E264Mb the residual needs, as they are */
+	uint32_t coded;
+	uint32_t payload_off;
+	uint16_t nz_mask;
+	uint16_t zero;
+} E264MbCompactTail;
+/* E264Mb.flags an entry may carry (any other keeps the full record): without / with the tail */
+#define E264_MBCF_PLAIN (E264_MBF_EDGE_LEFT | E264_MBF_EDGE_TOP | E264_MBF_DEBLOCK)
+#define E264_MBCF_RESID (E264_MBCF_PLAIN | E264_MBF_T8x8 | E264_MBF_LEV8)
+/* class of an entry: 0 the full record; else 1 (one list) or 2 (both lists), plus E264_CLS_RESID when the tail follows */
+#define E264_CLS_RESID 4
 E264_SIZE_CHECK(sizeof(E264CompactHdr) == 16, "E264CompactHdr");
+E264_SIZE_CHECK(sizeof(E264CompactHdr2) == 24, "E264CompactHdr2");
+E264_SIZE_CHECK(sizeof(E264MbCompactTail) == 12, "E264MbCompactTail");
 E264_SIZE_CHECK(sizeof(E264MbCompact) == 12, "E264MbCompact");
 E264_SIZE_CHECK(sizeof(E264MbCompactL1) == 8, "E264MbCompactL1");
 
-static inline uint32_t e264_compact_table_bytes(uint32_t width_mbs, uint32_t height_mbs)
-{ /* header + directory + bitmaps, padded to 8: where the entry area starts (from mbs_off) */
+static inline uint32_t e264_compact_entry_bytes(int cls) { return cls == 0 ? 32u : 4u + 8u * ((uint32_t)cls & 3u) + 3u * ((uint32_t)cls & E264_CLS_RESID); } /* 32 | 12, 20, 24, 32 */
+static inline uint32_t e264_compact_hdr_bytes(int level) { return level == 2 ? 24u : 16u; }
+static inline uint32_t e264_compact_table_bytes(uint32_t width_mbs, uint32_t height_mbs, int level)
+{ /* header + directory + bitmaps (two, three at level 2), padded to 8: where the entry area starts (from mbs_off) */
 	const uint32_t wpr = (width_mbs + 31u) >> 5;
-	return (16u + 12u * height_mbs + 8u * height_mbs * wpr + 7u) & ~7u;
+	return (e264_compact_hdr_bytes(level) + 12u * height_mbs + (level == 2 ? 12u : 8u) * height_mbs * wpr + 7u) & ~7u;
 }
 
-/* how can this version-4 record go?  0: as it is, 1: one-list entry, 2: two-list entry.  rec: its motion record (NULL when the packet has no motion section) */
-static inline int e264_mb_compact_class(const E264Mb *m, const uint8_t *rec)
+/* how can this version-4 record go at this level of the fold?  The class of its entry (0: as it is).  rec: its motion record (NULL when the packet has no
+ * motion section) */
+static inline int e264_mb_compact_class(const E264Mb *m, const uint8_t *rec, int level)
 {
 	uint32_t d[2], r0, r1;
-	if (m->kind != E264_MB_INTER || (m->flags & ~(E264_MBF_EDGE_LEFT | E264_MBF_EDGE_TOP | E264_MBF_DEBLOCK)) || m->coded || m->nz_mask || m->slice > 255 || m->dbk_slice > 255 || !rec)
+	if (m->kind != E264_MB_INTER || m->slice > 255 || m->dbk_slice > 255 || !rec)
 		return 0;
+	int resid = 0;
+	if ((m->flags & ~E264_MBCF_PLAIN) || m->coded || m->nz_mask) { /* level 1: nothing but edge flags, no residual */
+		if (level < 2 || (m->flags & ~E264_MBCF_RESID))
+			return 0;
+		resid = E264_CLS_RESID;
+	}
 	memcpy(d, m->modes, 8);
 	memcpy(&r0, rec, 4);
 	if (r0 & 0xffffe0e0u) /* slot and index below 32, the two spare bytes zero */
 		return 0;
 	if (d[1] == E264_MOT_HDR_UNI0 || d[1] == E264_MOT_HDR_UNI1)
-		return 1;
+		return 1 | resid;
 	if (d[1] != E264_MOT_HDR_UNI01)
 		return 0;
 	memcpy(&r1, rec + 8, 4);
-	return (r1 & 0xffffe0e0u) ? 0 : 2;
+	return (r1 & 0xffffe0e0u) ? 0 : 2 | resid;
 }
 
 /* upper bound of what e264_compact_packet / e264_compact_sections write for a picture whose version-4 packet has this header */
-static inline size_t e264_compact_bound(const void *v4)
+static inline size_t e264_compact_bound(const void *v4, int level)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)v4;
-	return (size_t)h->total_bytes + e264_compact_table_bytes(h->width_mbs, h->height_mbs) + 64;
+	return (size_t)h->total_bytes + e264_compact_table_bytes(h->width_mbs, h->height_mbs, level) + 64;
 }
 
-/* The fold, from the SECTIONS of a version-4 packet wherever they lie (a front end folds straight out of its builder's arrays; e264_compact_packet below
- * folds a packet).  h: the version-4 header (magic, sizes, slices_off, mbs_off, n_slices, payload_bytes and the summary fields are taken as they are;
- * motion_off, payload_off, total_bytes, version are written anew).  mot: NULL when no macroblock is inter.  payload_len <= h->payload_bytes bytes are
- * copied, the rest is zeros.  The sections must be what e264hip_packet_check would accept.  Returns the wire size, 0 when `cap` is too small. */
+/* The fold at `level` (1: version 5, 2: version 6), from the SECTIONS of a version-4 packet wherever they lie (a front end folds straight out of its builder's
+ * arrays; e264_compact_packet below folds a packet).  h: the version-4 header (magic, sizes, slices_off, mbs_off, n_slices, payload_bytes and the summary fields
+ * are taken as they are; motion_off, payload_off, total_bytes, version are written anew).  mot: NULL when no macroblock is inter.  payload_len <=
+ * h->payload_bytes bytes are copied, the rest is zeros.  The sections must be what e264hip_packet_check would accept.  Returns the wire size, 0 when `cap` is
+ * too small or the level is neither. */
 static inline size_t e264_compact_sections(const E264FrameHdr *h, const void *slices, const E264Mb *mbs, const uint8_t *mot, const uint8_t *payload, size_t payload_len,
-	void *out, size_t cap)
+	int level, void *out, size_t cap)
 {
 	const uint32_t wm = h->width_mbs, hm = h->height_mbs, wpr = (wm + 31u) >> 5;
-	const uint32_t tb = e264_compact_table_bytes(wm, hm);
-	if (cap < (size_t)h->total_bytes + tb + 64)
+	const uint32_t tb = e264_compact_table_bytes(wm, hm, level);
+	if ((level != 1 && level != 2) || cap < (size_t)h->total_bytes + tb + 64)
 		return 0;
 	uint8_t *o = (uint8_t *)out;
 	memcpy(o, h, sizeof(*h));
@@ -115,10 +155,11 @@ static inline size_t e264_compact_sections(const E264FrameHdr *h, const void *sl
 	const uint32_t send = h->slices_off + (uint32_t)sizeof(E264SliceParams) * h->n_slices;
 	memset(o + send, 0, h->mbs_off - send + tb);
 	E264FrameHdr *oh = (E264FrameHdr *)o;
-	E264CompactHdr *ch = (E264CompactHdr *)(o + h->mbs_off);
-	uint32_t *row_off = (uint32_t *)(o + h->mbs_off + 16), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm, *bbits = cbits + hm * wpr;
+	E264CompactHdr2 *ch = (E264CompactHdr2 *)(o + h->mbs_off); /* (level 1: its first 16 bytes) */
+	uint32_t *row_off = (uint32_t *)(o + h->mbs_off + e264_compact_hdr_bytes(level)), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm,
+		*bbits = cbits + hm * wpr, *rbits = bbits + hm * wpr; /* (rbits: level 2 only) */
 	uint8_t *ent = o + h->mbs_off + tb;
-	uint32_t eoff = 0, nc = 0, nb = 0, moff = 0;
+	uint32_t eoff = 0, nc = 0, nb = 0, nr = 0, moff = 0;
 	const E264Mb *m = mbs;
 	for (uint32_t y = 0; y < hm; y++) {
 		row_off[y] = eoff; row_cbase[y] = nc; row_bbase[y] = nb;
@@ -127,7 +168,7 @@ static inline size_t e264_compact_sections(const E264FrameHdr *h, const void *sl
 			uint32_t d[2];
 			memcpy(d, m->modes, 8);
 			const uint8_t *rec = mot ? mot + d[0] : NULL;
-			const int cls = e264_mb_compact_class(m, rec);
+			const int cls = e264_mb_compact_class(m, rec, level);
 			if (!cls) {
 				memcpy(ent + eoff, m, 32);
 				memcpy(ent + eoff + offsetof(E264Mb, modes), &moff, 4); /* mot_off in this packet's motion section */
@@ -141,14 +182,21 @@ static inline size_t e264_compact_sections(const E264FrameHdr *h, const void *sl
 			memcpy(c + 8, rec + 4, 4);
 			eoff += 12; nc++;
 			cbits[y * wpr + (x >> 5)] |= 1u << (x & 31);
-			if (cls == 2) {
+			if ((cls & 3) == 2) {
 				memcpy(c + 12, rec + 8, 8);
 				eoff += 8; nb++;
 				bbits[y * wpr + (x >> 5)] |= 1u << (x & 31);
 			}
+			if (cls & E264_CLS_RESID) {
+				const E264MbCompactTail t = {m->coded, m->payload_off, m->nz_mask, 0};
+				memcpy(ent + eoff, &t, 12);
+				eoff += 12; nr++;
+				rbits[y * wpr + (x >> 5)] |= 1u << (x & 31);
+			}
 		}
 	}
 	ch->n_compact = nc; ch->n_both = nb; ch->entries_bytes = eoff; ch->words_per_row = wpr;
+	if (level == 2) ch->n_resid = nr;
 	/* motion section: the records of the full inter macroblocks, in macroblock order (the bitmap says which are not) */
 	uint32_t pos = (h->mbs_off + tb + eoff + 7u) & ~7u;
 	memset(ent + eoff, 0, pos - (h->mbs_off + tb + eoff));
@@ -170,54 +218,58 @@ static inline size_t e264_compact_sections(const E264FrameHdr *h, const void *sl
 	pos += pad;
 	if (payload_len) memcpy(o + pos, payload, payload_len);
 	memset(o + pos + payload_len, 0, h->payload_bytes - payload_len);
-	oh->version = E264_VERSION_COMPACT;
+	oh->version = level == 2 ? E264_VERSION_COMPACT2 : E264_VERSION_COMPACT;
 	oh->payload_off = pos;
 	oh->total_bytes = pos + h->payload_bytes;
 	return oh->total_bytes;
 }
 
-/* version 4 (already vetted: e264hip_packet_check, or the front end's own product) -> version 5.  Returns the wire size, 0 when `cap` is too small or the
- * input is not a version-4 packet. */
-static inline size_t e264_compact_packet(const void *v4, size_t bytes, void *out, size_t cap)
+/* version 4 (already vetted: e264hip_packet_check, or the front end's own product) -> version 5 (level 1) or 6 (level 2).  Returns the wire size, 0 when `cap`
+ * is too small, the input is not a version-4 packet or the level is neither. */
+static inline size_t e264_compact_packet(const void *v4, size_t bytes, int level, void *out, size_t cap)
 {
 	const uint8_t *p = (const uint8_t *)v4;
 	const E264FrameHdr *h = (const E264FrameHdr *)v4;
 	if (bytes < sizeof(*h) || h->magic != E264_MAGIC || h->version != E264_VERSION)
 		return 0;
-	return e264_compact_sections(h, p + h->slices_off, (const E264Mb *)(p + h->mbs_off), h->motion_off ? p + h->motion_off : NULL, p + h->payload_off, h->payload_bytes, out, cap);
+	return e264_compact_sections(h, p + h->slices_off, (const E264Mb *)(p + h->mbs_off), h->motion_off ? p + h->motion_off : NULL, p + h->payload_off, h->payload_bytes, level, out, cap);
 }
 
-/* Structure of a version-5 packet: everything an expansion (host or device) reads lies inside the packet and says what the bitmaps say.  0 = sound.
- * (What the records then MEAN is vetted on the expanded packet by the back end's per-macroblock walk, as for version 4.) */
+/* Structure of a wire packet (version 5 or 6, as its header says): everything an expansion (host or device) reads lies inside the packet and says what the
+ * bitmaps say.  0 = sound.  (What the records then MEAN is vetted on the expanded packet by the back end's per-macroblock walk, as for version 4.) */
 static inline int e264_check_compact(const void *wire, size_t bytes)
 {
 	const uint8_t *p = (const uint8_t *)wire;
 	const E264FrameHdr *h = (const E264FrameHdr *)wire;
-	if (bytes < sizeof(*h) || h->magic != E264_MAGIC || h->version != E264_VERSION_COMPACT || h->total_bytes != bytes) return -1;
+	if (bytes < sizeof(*h) || h->magic != E264_MAGIC || !e264_wire_level(h->version) || h->total_bytes != bytes) return -1;
+	const int level = e264_wire_level(h->version);
 	const uint32_t wm = h->width_mbs, hm = h->height_mbs;
 	if (wm == 0 || hm == 0 || hm > 1056) return -1;
 	const uint64_t n = (uint64_t)wm * hm;
-	const uint32_t wpr = (wm + 31u) >> 5, tb = e264_compact_table_bytes(wm, hm);
+	const uint32_t wpr = (wm + 31u) >> 5, tb = e264_compact_table_bytes(wm, hm, level);
 	if ((h->mbs_off & 7) || (uint64_t)h->slices_off + (uint64_t)h->n_slices * sizeof(E264SliceParams) > h->mbs_off || (uint64_t)h->mbs_off + tb > bytes) return -1;
-	const E264CompactHdr *ch = (const E264CompactHdr *)(p + h->mbs_off);
-	if (ch->words_per_row != wpr || ch->n_compact > n || ch->n_both > ch->n_compact || ch->entries_bytes != 32ull * n - 20ull * ch->n_compact + 8ull * ch->n_both) return -1;
+	const E264CompactHdr2 *ch = (const E264CompactHdr2 *)(p + h->mbs_off); /* (version 5: its first 16 bytes) */
+	const uint32_t n_resid = level == 2 ? ch->n_resid : 0;
+	if (level == 2 && (ch->zero || n_resid > ch->n_compact)) return -1;
+	if (ch->words_per_row != wpr || ch->n_compact > n || ch->n_both > ch->n_compact || ch->entries_bytes != 32ull * n - 20ull * ch->n_compact + 8ull * ch->n_both + 12ull * n_resid) return -1;
 	const uint64_t end = (uint64_t)h->mbs_off + tb + ch->entries_bytes;
 	if (end > bytes || (h->motion_off && (h->motion_off < end || h->motion_off > bytes)) || h->payload_off < end || (uint64_t)h->payload_off + h->payload_bytes > bytes) return -1;
 	if ((h->motion_off && h->motion_off > h->payload_off) || ((h->slices_off | h->motion_off | h->payload_off) & 7)) return -1;
-	const uint32_t *row_off = (const uint32_t *)(p + h->mbs_off + 16), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm, *bbits = cbits + (size_t)hm * wpr;
-	uint32_t eoff = 0, nc = 0, nb = 0;
+	const uint32_t *row_off = (const uint32_t *)(p + h->mbs_off + e264_compact_hdr_bytes(level)), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm,
+		*bbits = cbits + (size_t)hm * wpr, *rbits = bbits + (size_t)hm * wpr;
+	uint32_t eoff = 0, nc = 0, nb = 0, nr = 0;
 	for (uint32_t y = 0; y < hm; y++) {
 		if (row_off[y] != eoff || row_cbase[y] != nc || row_bbase[y] != nb) return -1;
-		uint32_t c = 0, b = 0;
+		uint32_t c = 0, b = 0, r = 0;
 		for (uint32_t w = 0; w < wpr; w++) {
-			const uint32_t cw = cbits[y * wpr + w], bw = bbits[y * wpr + w];
+			const uint32_t cw = cbits[y * wpr + w], bw = bbits[y * wpr + w], rw = level == 2 ? rbits[y * wpr + w] : 0;
 			if (w == wpr - 1 && (wm & 31) && (cw >> (wm & 31))) return -1; /* bits beyond the row */
-			if (bw & ~cw) return -1;
-			c += (uint32_t)__builtin_popcount(cw); b += (uint32_t)__builtin_popcount(bw);
+			if ((bw | rw) & ~cw) return -1;
+			c += (uint32_t)__builtin_popcount(cw); b += (uint32_t)__builtin_popcount(bw); r += (uint32_t)__builtin_popcount(rw);
 		}
-		nc += c; nb += b; eoff += 32 * wm - 20 * c + 8 * b;
+		nc += c; nb += b; nr += r; eoff += 32 * wm - 20 * c + 8 * b + 12 * r;
 	}
-	if (nc != ch->n_compact || nb != ch->n_both || eoff != ch->entries_bytes) return -1;
+	if (nc != ch->n_compact || nb != ch->n_both || nr != n_resid || eoff != ch->entries_bytes) return -1;
 	/* the expansion is a version-4 packet: 32-bit offsets (and what the kernels add to them) */
 	return ((uint64_t)h->mbs_off + 32 * n + (h->motion_off ? h->payload_off - h->motion_off : 0) + 8ull * nc + 8ull * nb + 8 + h->payload_bytes) >> 31 ? -1 : 0;
 }
@@ -230,7 +282,8 @@ static inline size_t e264_expanded_motion_bytes(const void *wire)
 	const E264CompactHdr *ch = (const E264CompactHdr *)(p + h->mbs_off);
 	return (size_t)(h->motion_off ? h->payload_off - h->motion_off : 0) + (size_t)8 * ch->n_compact + (size_t)8 * ch->n_both; /* (all three multiples of 8) */
 }
-/* size of the canonical version-4 packet e264_expand_packet makes of this (structurally sound) version-5 packet */
+/* size of the canonical version-4 packet e264_expand_packet makes of this (structurally sound) wire packet, of either version: the residual tails of
+ * version 6 go into records that are there anyway */
 static inline size_t e264_expanded_bytes(const void *wire)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)wire;
@@ -244,10 +297,11 @@ static inline size_t e264_expand_area_bytes(const void *wire)
 	return (size_t)32 * h->width_mbs * h->height_mbs + e264_expanded_motion_bytes(wire);
 }
 
-/* A compact entry (one list: 12 bytes, `both` lists: 20) as what it stands for: the version-4 record, whose motion record lies at mot_off of the motion section,
- * and that motion record (rec; returns its 8 or 16 bytes). */
-static inline uint32_t e264_compact_entry_expand(const uint8_t *e, int both, uint32_t mot_off, E264Mb *out, uint8_t rec[16])
+/* A compact entry of class `cls` (12, 20, 24 or 32 bytes) as what it stands for: the version-4 record, whose motion record lies at mot_off of the motion
+ * section, and that motion record (rec; returns its 8 or 16 bytes). */
+static inline uint32_t e264_compact_entry_expand(const uint8_t *e, int cls, uint32_t mot_off, E264Mb *out, uint8_t rec[16])
 {
+	const int both = (cls & 3) == 2;
 	E264MbCompact k;
 	memcpy(&k, e, 12);
 	memset(out, 0, 32);
@@ -259,13 +313,35 @@ static inline uint32_t e264_compact_entry_expand(const uint8_t *e, int both, uin
 	rec[0] = k.ref_slot; rec[1] = k.ref_idx; rec[2] = rec[3] = 0;
 	memcpy(rec + 4, k.mv, 4);
 	if (both) memcpy(rec + 8, e + 12, 8);
+	if (cls & E264_CLS_RESID) {
+		E264MbCompactTail t;
+		memcpy(&t, e + (both ? 20 : 12), 12);
+		out->coded = t.coded; out->payload_off = t.payload_off; out->nz_mask = t.nz_mask;
+	}
 	return both ? 16 : 8;
 }
 
-/* The entries of a (structurally sound) version-5 packet one after the other, in raster order: the sequential form of e264_expand_mb's address arithmetic,
+/* Is this entry of a version-6 packet the one the fold writes for the record it expands to?  Every spare bit zero (flag bits an entry may not carry, slot and
+ * index below 32, E264MbCompactL1.zero, E264MbCompactTail.zero), and a tail only where the plain entry could not say it: then folding the expansion again
+ * gives the packet's own bytes.  1 = it is. */
+static inline int e264_compact_entry_canonical(const uint8_t *e, int cls)
+{
+	const int both = (cls & 3) == 2;
+	uint32_t e0, l1 = 0;
+	memcpy(&e0, e, 4);
+	if (both) memcpy(&l1, e + 12, 4);
+	if ((e0 & 0x00e0e000u) || (l1 & 0xffffe0e0u)) return 0;
+	const uint32_t flags = e0 & 0x7fu;
+	if (!(cls & E264_CLS_RESID)) return !(flags & ~(uint32_t)E264_MBCF_PLAIN);
+	E264MbCompactTail t;
+	memcpy(&t, e + (both ? 20 : 12), 12);
+	return !(flags & ~(uint32_t)E264_MBCF_RESID) && !t.zero && ((flags & ~(uint32_t)E264_MBCF_PLAIN) || t.coded || t.nz_mask);
+}
+
+/* The entries of a (structurally sound) wire packet one after the other, in raster order: the sequential form of e264_expand_mb's address arithmetic,
  * running counts instead of popcounts. */
 typedef struct E264CompactCursor {
-	const uint32_t *cbits, *bbits; /* bitmap words of the current row */
+	const uint32_t *cbits, *bbits, *rbits; /* bitmap words of the current row (rbits: NULL in version 5) */
 	const uint8_t *e;              /* the next entry */
 	uint32_t x, wm, wpr;
 	uint32_t nc, nb;               /* compact / two-list macroblocks before it: its motion record lies 8 * (nc + nb) bytes behind the first compact one's */
@@ -273,45 +349,54 @@ typedef struct E264CompactCursor {
 static inline void e264_cursor_init(E264CompactCursor *c, const uint8_t *wire)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)wire;
+	const int level = e264_wire_level(h->version);
 	c->x = c->nc = c->nb = 0;
 	c->wm = h->width_mbs; c->wpr = ((const E264CompactHdr *)(wire + h->mbs_off))->words_per_row;
-	c->cbits = (const uint32_t *)(wire + h->mbs_off + 16) + 3 * (size_t)h->height_mbs;
+	c->cbits = (const uint32_t *)(wire + h->mbs_off + e264_compact_hdr_bytes(level)) + 3 * (size_t)h->height_mbs;
 	c->bbits = c->cbits + (size_t)h->height_mbs * c->wpr;
-	c->e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, h->height_mbs);
+	c->rbits = level == 2 ? c->bbits + (size_t)h->height_mbs * c->wpr : NULL;
+	c->e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, h->height_mbs, level);
 }
-/* the next macroblock's entry (*entry) and its class: 0 full record (32 bytes), 1 one list (12), 2 both lists (20) */
+/* the next macroblock's entry (*entry) and its class: 0 full record (32 bytes), 1 one list (12), 2 both lists (20), with E264_CLS_RESID 12 more */
 static inline int e264_cursor_next(E264CompactCursor *c, const uint8_t **entry)
 {
 	const uint32_t w = c->x >> 5, bit = c->x & 31;
-	const int cls = (int)(c->cbits[w] >> bit & 1u) + (int)(c->bbits[w] >> bit & 1u); /* (bbits is a subset of cbits) */
+	int cls = (int)(c->cbits[w] >> bit & 1u) + (int)(c->bbits[w] >> bit & 1u); /* (bbits is a subset of cbits) */
+	if (c->rbits && (c->rbits[w] >> bit & 1u)) cls |= E264_CLS_RESID;           /* (so is rbits) */
 	*entry = c->e;
-	c->e += cls == 0 ? 32 : cls == 1 ? 12 : 20;
-	c->nc += cls > 0; c->nb += cls > 1;
-	if (++c->x == c->wm) { c->x = 0; c->cbits += c->wpr; c->bbits += c->wpr; }
+	c->e += e264_compact_entry_bytes(cls);
+	c->nc += cls > 0; c->nb += (cls & 3) > 1;
+	if (++c->x == c->wm) { c->x = 0; c->cbits += c->wpr; c->bbits += c->wpr; if (c->rbits) c->rbits += c->wpr; }
 	return cls;
 }
 
-/* the version-4 record of macroblock (x, y) of a version-5 packet and, for a compact one, its motion record (8 or 16 bytes, *rec_bytes; 0 for a full record).
+/* the version-4 record of macroblock (x, y) of a wire packet and, for a compact one, its motion record (8 or 16 bytes, *rec_bytes; 0 for a full record).
  * synth_off: mot_off of the FIRST compact macroblock's motion record (they follow one another in macroblock order).  THE definition of the expansion: the
  * device kernel restates it. */
 static inline void e264_expand_mb(const uint8_t *wire, uint32_t x, uint32_t y, uint32_t synth_off, E264Mb *out, uint8_t rec[16], uint32_t *rec_bytes)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)wire;
 	const E264CompactHdr *ch = (const E264CompactHdr *)(wire + h->mbs_off);
+	const int level = e264_wire_level(h->version);
 	const uint32_t hm = h->height_mbs, wpr = ch->words_per_row;
-	const uint32_t *row_off = (const uint32_t *)(wire + h->mbs_off + 16), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm, *bbits = cbits + hm * wpr;
-	uint32_t c = 0, b = 0;
-	for (uint32_t w = 0; w < (x >> 5); w++) { c += (uint32_t)__builtin_popcount(cbits[y * wpr + w]); b += (uint32_t)__builtin_popcount(bbits[y * wpr + w]); }
-	const uint32_t cw = cbits[y * wpr + (x >> 5)], bw = bbits[y * wpr + (x >> 5)], below = (1u << (x & 31)) - 1u;
-	c += (uint32_t)__builtin_popcount(cw & below); b += (uint32_t)__builtin_popcount(bw & below);
-	const uint8_t *e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, hm) + row_off[y] + 32u * x - 20u * c + 8u * b;
+	const uint32_t *row_off = (const uint32_t *)(wire + h->mbs_off + e264_compact_hdr_bytes(level)), *row_cbase = row_off + hm, *row_bbase = row_cbase + hm, *cbits = row_bbase + hm,
+		*bbits = cbits + hm * wpr, *rbits = level == 2 ? bbits + hm * wpr : NULL;
+	uint32_t c = 0, b = 0, r = 0;
+	for (uint32_t w = 0; w < (x >> 5); w++) {
+		c += (uint32_t)__builtin_popcount(cbits[y * wpr + w]); b += (uint32_t)__builtin_popcount(bbits[y * wpr + w]);
+		if (rbits) r += (uint32_t)__builtin_popcount(rbits[y * wpr + w]);
+	}
+	const uint32_t cw = cbits[y * wpr + (x >> 5)], bw = bbits[y * wpr + (x >> 5)], rw = rbits ? rbits[y * wpr + (x >> 5)] : 0, below = (1u << (x & 31)) - 1u;
+	c += (uint32_t)__builtin_popcount(cw & below); b += (uint32_t)__builtin_popcount(bw & below); r += (uint32_t)__builtin_popcount(rw & below);
+	const uint8_t *e = wire + h->mbs_off + e264_compact_table_bytes(h->width_mbs, hm, level) + row_off[y] + 32u * x - 20u * c + 8u * b + 12u * r;
 	*rec_bytes = 0;
 	if (!(cw >> (x & 31) & 1u)) { memcpy(out, e, 32); return; }
-	*rec_bytes = e264_compact_entry_expand(e, (int)(bw >> (x & 31) & 1u), synth_off + 8u * (row_cbase[y] + c) + 8u * (row_bbase[y] + b), out, rec);
+	const int cls = 1 + (int)(bw >> (x & 31) & 1u) + ((rw >> (x & 31) & 1u) ? E264_CLS_RESID : 0);
+	*rec_bytes = e264_compact_entry_expand(e, cls, synth_off + 8u * (row_cbase[y] + c) + 8u * (row_bbase[y] + b), out, rec);
 }
 
-/* version 5 (e264_check_compact has said 0) -> canonical version 4: [header][slices][E264Mb x n][motion: the wire's records, then the compact macroblocks'][payload].
- * Returns the size, 0 when `cap` is too small. */
+/* version 5 or 6 (e264_check_compact has said 0) -> canonical version 4: [header][slices][E264Mb x n][motion: the wire's records, then the compact
+ * macroblocks'][payload].  Returns the size, 0 when `cap` is too small. */
 static inline size_t e264_expand_packet(const void *wire, size_t bytes, void *out, size_t cap)
 {
 	const uint8_t *p = (const uint8_t *)wire;
