@@ -68,6 +68,12 @@ class RefKernels:
     """The reference's static kernels replaying a packet (oracle/ref_kernels_harness.c)."""
 
     def __init__(self):
+        # where the reference tree exists the library follows ref_kernels_harness.c (oracle/Makefile: nothing to do when it is current, and
+        # nothing at all without the tree); a harness left over from another commit would pin the oracle to that commit's replay
+        try:
+            subprocess.run(["make", "-s", "-C", HERE, "harness"], check=False, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        except OSError:  # (no make: the library is taken as it is, like everywhere without the tree)
+            pass
         self.lib = _load(os.path.join(HERE, "_ref", "libe264_refkernels.so"))
         L = self.lib
         L.ref_new.argtypes = [C.c_int, C.c_int]

@@ -158,6 +158,8 @@ EXPORT int ref_replay_packet(RefHarness *h, const uint8_t *pkt, size_t bytes, ui
 				load_slice(ctx, s);
 				set_pos(h, fh, cur, mbx, mby);
 				ctx->t.QP[0] = m->qp[0]; ctx->t.QP[1] = m->qp[1]; ctx->t.QP[2] = m->qp[2];
+				if (m->flags & E264_MBF_DONE) /* an earlier packet of the picture wrote it (I_PCM too: the record carries no payload) */
+					continue;
 				const uint8_t *pl = payload + m->payload_off;
 				if (m->kind == E264_MB_PCM) {
 					for (int y = 0; y < 16; y++) memcpy(ctx->samples_mb[0] + y * fh->stride_Y, pl + y * 16, 16);
@@ -180,8 +182,6 @@ EXPORT int ref_replay_packet(RefHarness *h, const uint8_t *pkt, size_t bytes, ui
 					for (int i = 0; i < n; i++) wide[i] = (int8_t)pl[i];
 					co = wide;
 				}
-				if (m->flags & E264_MBF_DONE)
-					continue;
 				size_t sY = fh->stride_Y;
 				i16x8 clip = ctx->t.samples_clip_v[0];
 

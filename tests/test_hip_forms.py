@@ -25,6 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CORPUS = os.path.join(HERE, "golden", "corpus", "gpu_corpus_sample.zip")
 DEFAULTS = dict(split_planes=1, split_intra=1, side_queue=0, waves=108, intra_waves=16)
 HOWS = ["resident", "host", "pinned", "pinned_untrusted"]
+WIRE_VERSIONS = (P.E264_VERSION_COMPACT, P.E264_VERSION_COMPACT2)  # both levels of the fold go through the expansion kernel
 
 
 # ---- the launcher's rules, written out -------------------------------------------------------------------------
@@ -37,7 +38,7 @@ def packet_info(v4: bytes, sent: bytes, how: str):
     inter = np.nonzero(kind == P.MB_INTER)[0]
     l1 = bool(len(inter) and (pk.motion["refPic"][inter, 4:] >= 0).any())
     pw = bool(len(inter) or (kind == P.MB_PCM).any())
-    if how == "pinned" and sent[4] == P.E264_VERSION_COMPACT:
+    if how == "pinned" and sent[4] in WIRE_VERSIONS:
         pw = True
     return pw, l1
 
@@ -192,7 +193,7 @@ def run_batch(dev, oracle, how, decs, v4s, cfg, sent=None, max_lane=0, label="")
 def expected_submission(dev, how, v4s, sent, cfg, max_lane=0):
     """the forms one submission of v4s (sent: the bytes submitted) must launch, by entry point"""
     cus = dev.launch_counts()["n_cus"]
-    wire = [s[4] == P.E264_VERSION_COMPACT for s in sent]
+    wire = [s[4] in WIRE_VERSIONS for s in sent]
     if how == "single":  # (one launch per picture)
         want = Counter()
         for p, s, x in zip(v4s, sent, wire):

@@ -10,7 +10,7 @@ import pytest
 
 from edge264_amd import packet as P
 from edge264_amd import synth
-from tests import edge_cases, layouts, structure_cases
+from tests import edge_cases, layouts, split_cases, structure_cases
 
 W, H = 6, 5
 ALL_I = (P.MB_I8x8, P.MB_I4x4, P.MB_I16x16)
@@ -154,6 +154,30 @@ def test_saturated_structure(oracle, refkernels, name, w, h):
     _, _, pattern, kw, _ = structure_cases.CASES[name]
     structure_cases.check(name, w, h)  # (the packets run_stream makes from the same seed and options: their census)
     run_stream(oracle, refkernels, structure_cases.seed_of(name, w, h), pattern, kw, w, h)
+
+
+SPLIT = [(shape, w, h) for shape in split_cases.SHAPES for (w, h) in ((6, 5), (17, 5))]
+
+
+@pytest.mark.parametrize("shape,w,h", SPLIT, ids=[f"{s}_{w}x{h}" for s, w, h in SPLIT])
+def test_split_pictures(oracle, refkernels, shape, w, h):
+    """Pictures sent in several packets (tests/split_cases.py: E264_MBF_DONE records beside fresh ones, macroblocks deblocked by a later packet than the
+    one that reconstructed them), the rich stream, its census held against the shape's minimum: compared after every packet's reconstruction pass and
+    again after its deblocking.  A DONE I_PCM record has no payload: a harness that copied one from payload offset 0 would overwrite what the
+    earlier packet finished."""
+    from tests.test_hip_parity import describe_mismatch
+    pkts, labels = split_cases.flat(split_cases.packets(shape, "rich", w, h))
+    nb = P.frame_bytes(w, h)
+    rng = np.random.default_rng(w + h)
+    dpb_o = [rng.integers(0, 256, nb + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
+    dpb_r = [a.copy() if a is not None else None for a in dpb_o]
+    for pkt, label in zip(pkts, labels):
+        d = int(P.Packet(pkt).hdr["dst_slot"])
+        for passes in (1, 2):
+            oracle.decode_frame(pkt, dpb_o, passes)
+            refkernels.replay(pkt, dpb_r, w, h, passes)
+            assert np.array_equal(dpb_o[d], dpb_r[d]), f"{shape} {w}x{h} packet {label} pass {passes}, oracle / reference kernels: " + \
+                describe_mismatch(P.Packet(pkt), dpb_o[d][:nb], dpb_r[d][:nb], w, h)
 
 
 LAYOUT_CASES = [c for c in CASES if c[0] in ("intra8x8", "pcm", "ibbp_explicit_wp", "ibbp_implicit_wp", "slices_idc2", "stress_implicit_far_mv")]
