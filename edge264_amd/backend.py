@@ -61,6 +61,8 @@ def load_library():
         "e264hip_packet_compact": (sz, [vp, sz, vp, sz]),
         "e264hip_packet_compact2_bound": (sz, [vp, sz, i]),
         "e264hip_packet_compact2": (sz, [vp, sz, i, vp, sz]),
+        "e264hip_packet_fold_bound": (sz, [vp, sz, i]),
+        "e264hip_packet_fold": (sz, [vp, sz, i, vp, sz]),
         "e264hip_packet_expand": (sz, [vp, sz, vp, sz]),
         "e264hip_submit_batch_host": (i, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), i, i]),
         "e264hip_submit_batch_pinned": (i, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), i, i, i]),
@@ -100,7 +102,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_stream_open", "e264hip_stream_close", "e264hip_stream_bind_lane", "e264hip_stream_flush", "e264hip_frame_alloc",
     "e264hip_frame_free", "e264hip_frame_fill", "e264hip_frame_upload", "e264hip_frame_submit",
     "e264hip_packet_buffer", "e264hip_frame_wait", "e264hip_frame_download", "e264hip_packet_upload",
-    "e264hip_packet_free", "e264hip_packet_check", "e264hip_packet_compact_bound", "e264hip_packet_compact", "e264hip_packet_compact2_bound", "e264hip_packet_compact2", "e264hip_packet_expand", "e264hip_submit_batch", "e264hip_submit_batch_host", "e264hip_submit_batch_pinned", "e264hip_host_alloc", "e264hip_host_free", "e264hip_batch_create", "e264hip_batch_submit", "e264hip_batch_free", "e264hip_event_record", "e264hip_event_elapsed_ms", "e264hip_event_query",
+    "e264hip_packet_free", "e264hip_packet_check", "e264hip_packet_compact_bound", "e264hip_packet_compact", "e264hip_packet_compact2_bound", "e264hip_packet_compact2", "e264hip_packet_fold_bound", "e264hip_packet_fold", "e264hip_packet_expand", "e264hip_submit_batch", "e264hip_submit_batch_host", "e264hip_submit_batch_pinned", "e264hip_host_alloc", "e264hip_host_free", "e264hip_batch_create", "e264hip_batch_submit", "e264hip_batch_free", "e264hip_event_record", "e264hip_event_elapsed_ms", "e264hip_event_query",
     "e264hip_kernel_timing", "e264hip_kernel_time_ms", "e264hip_set_option", "e264hip_build_flags", "e264hip_frame_device_ptr",
     "e264hip_launch_counts",
 ]
@@ -135,6 +137,19 @@ def packet_compact(pkt: bytes, level: int = 1) -> bytes:
     n = L.e264hip_packet_compact2(C.cast(src, C.c_void_p), len(pkt), level, C.cast(out, C.c_void_p), cap) if cap else 0
     if not n:
         raise BackendError(f"packet_compact: {last_error()}")
+    return bytes(out[:n])
+
+
+def packet_fold(pkt: bytes, level: int) -> bytes:
+    """A version-4 packet folded at `level` of the WIRE form: 1 and 2 give the bytes of packet_compact, 3 gives version 7 (runs of equal plain entries
+    travel as one entry).  Host only."""
+    L = load_library()
+    src = (C.c_char * len(pkt)).from_buffer_copy(pkt)
+    cap = L.e264hip_packet_fold_bound(C.cast(src, C.c_void_p), len(pkt), level)
+    out = (C.c_char * max(cap, 1))()
+    n = L.e264hip_packet_fold(C.cast(src, C.c_void_p), len(pkt), level, C.cast(out, C.c_void_p), cap) if cap else 0
+    if not n:
+        raise BackendError(f"packet_fold: {last_error()}")
     return bytes(out[:n])
 
 

@@ -117,19 +117,23 @@ int e264_check_records(const void *packet, E264SlotView slots, E264PacketInfo *i
 	if (e264_wire_level(h->version)) {
 		// A wire packet (include/edge264_compact.h; e264_check_header has vetted its structure) means what its expansion means: every entry is held
 		// against the same checks as the version-4 record e264_expand_kernel will make of it -- walked in place, entry by entry, without unfolding the packet.
-		// Version 6 is held to the canonical form as well (spare bits zero, a tail only where it says something): folding its expansion again gives its own bytes.
-		const bool v6 = h->version == E264_VERSION_COMPACT2;
+		// Versions 6 and 7 are held to the canonical form as well (spare bits zero, a tail only where it says something, in version 7 no plain entry that equals
+		// its left neighbour's and so should have been a repeat): folding the expansion again gives the packet's own bytes.  A repeat of version 7 is checked as
+		// the record it expands to, at its own address: the entry is its source's.
+		const int level = e264_wire_level(h->version);
 		E264CompactCursor c;
 		e264_cursor_init(&c, p);
-		for (int a = 0, r, n_mbs = info->n_mbs(), col = 0; a < n_mbs; a++, col = col + 1 == h->width_mbs ? 0 : col + 1) {
+		const uint8_t *left = nullptr; // version 7: the entry of the macroblock to the left in the row, of class left_cls
+		for (int a = 0, r, n_mbs = info->n_mbs(), col = 0, left_cls = 0; a < n_mbs; a++, col = col + 1 == h->width_mbs ? 0 : col + 1) {
 			const uint8_t *e;
 			const int cls = e264_cursor_next(&c, &e);
 			E264Mb m;
 			uint8_t rec[16];
 			if (!cls) { memcpy(&m, e, 32); r = check_mb(w, m, a, col, mot, mot_bytes); }
-			else if (v6 && !e264_compact_entry_canonical(e, cls)) r = fail(EINVAL, "wire entry not in canonical form");
+			else if (level >= 2 && !c.repeat && !e264_compact_entry_canonical(e, cls, col ? left : nullptr, left_cls)) r = fail(EINVAL, "wire entry not in canonical form");
 			else r = check_mb(w, m, a, col, rec, e264_compact_entry_expand(e, cls, 0, &m, rec));
 			if (r) return r;
+			if (level == 3) { left = e; left_cls = cls; }
 		}
 	} else {
 		const E264Mb *mbs = (const E264Mb *)(p + h->mbs_off);
@@ -202,25 +206,36 @@ API int e264hip_packet_check(const void *packet, size_t bytes)
 }
 
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.
-API size_t e264hip_packet_compact2_bound(const void *packet, size_t bytes, int level)
+// e264hip_packet_fold takes every level; _compact2 keeps what it took when it was written (1 and 2), _compact is level 1.
+API size_t e264hip_packet_fold_bound(const void *packet, size_t bytes, int level)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
-	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
+	if (level < 1 || level > 3) { fail(EINVAL, "packet_fold: level is none of 1, 2, 3"); return 0; }
 	return (packet && bytes >= sizeof(*h) && h->magic == E264_MAGIC && h->version == E264_VERSION) ? e264_compact_bound(packet, level) : 0;
 }
-API size_t e264hip_packet_compact_bound(const void *packet, size_t bytes) { return e264hip_packet_compact2_bound(packet, bytes, 1); }
-// version 4 -> version 5 (level 1) or 6 (level 2); the input must pass e264hip_packet_check (checked here).  Returns the size written, 0 on error (e264hip_last_error).
-API size_t e264hip_packet_compact2(const void *packet, size_t bytes, int level, void *out, size_t cap)
+// version 4 -> version 5 (level 1), 6 (level 2) or 7 (level 3); the input must pass e264hip_packet_check (checked here).  Returns the size written, 0 on error (e264hip_last_error).
+API size_t e264hip_packet_fold(const void *packet, size_t bytes, int level, void *out, size_t cap)
 {
 	const E264FrameHdr *h = (const E264FrameHdr *)packet;
-	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
-	if (!packet || !out || bytes < sizeof(*h) || h->version != E264_VERSION || e264hip_packet_check(packet, bytes)) { fail(EINVAL, "packet_compact: not a sound version-4 packet"); return 0; }
+	if (level < 1 || level > 3) { fail(EINVAL, "packet_fold: level is none of 1, 2, 3"); return 0; }
+	if (!packet || !out || bytes < sizeof(*h) || h->version != E264_VERSION || e264hip_packet_check(packet, bytes)) { fail(EINVAL, "packet_fold: not a sound version-4 packet"); return 0; }
 	const size_t r = e264_compact_packet(packet, h->total_bytes, level, out, cap);
-	if (!r) fail(EINVAL, "packet_compact: output buffer too small");
+	if (!r) fail(EINVAL, "packet_fold: output buffer too small");
 	return r;
 }
-API size_t e264hip_packet_compact(const void *packet, size_t bytes, void *out, size_t cap) { return e264hip_packet_compact2(packet, bytes, 1, out, cap); }
-// version 5 or 6 -> the canonical version-4 packet.  out == NULL: the size needed.  0 on error.
+API size_t e264hip_packet_compact2_bound(const void *packet, size_t bytes, int level)
+{
+	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
+	return e264hip_packet_fold_bound(packet, bytes, level);
+}
+API size_t e264hip_packet_compact_bound(const void *packet, size_t bytes) { return e264hip_packet_fold_bound(packet, bytes, 1); }
+API size_t e264hip_packet_compact2(const void *packet, size_t bytes, int level, void *out, size_t cap)
+{
+	if (level != 1 && level != 2) { fail(EINVAL, "packet_compact: level is neither 1 nor 2"); return 0; }
+	return e264hip_packet_fold(packet, bytes, level, out, cap);
+}
+API size_t e264hip_packet_compact(const void *packet, size_t bytes, void *out, size_t cap) { return e264hip_packet_fold(packet, bytes, 1, out, cap); }
+// version 5, 6 or 7 -> the canonical version-4 packet.  out == NULL: the size needed.  0 on error.
 API size_t e264hip_packet_expand(const void *packet, size_t bytes, void *out, size_t cap)
 {
 	E264PacketInfo info;

@@ -1,6 +1,6 @@
 // e264_check.h -- the gate in front of the GPU: what a command packet must satisfy before a kernel may read it.  Host code only (plain C++17, no HIP): it reads
 // hostile bytes, so tools/sanitize/kernel_fuzz.py builds and runs it under AddressSanitizer.  e264_check.cpp also holds the entry points of include/edge264_hip.h
-// that need no device (e264hip_packet_check, e264hip_packet_compact_bound, e264hip_packet_compact, e264hip_packet_compact2_bound, e264hip_packet_compact2, e264hip_packet_expand, e264hip_last_error).
+// that need no device (e264hip_packet_check, e264hip_packet_compact_bound, e264hip_packet_compact, e264hip_packet_compact2_bound, e264hip_packet_compact2, e264hip_packet_fold_bound, e264hip_packet_fold, e264hip_packet_expand, e264hip_last_error).
 #ifndef E264_CHECK_H
 #define E264_CHECK_H
 #include "../../include/edge264_hip.h"
@@ -17,7 +17,7 @@ int e264_fail(int code, const char *what, const char *detail = nullptr); // writ
 // e264_check_records and e264_scan_trusted then set pred_work and has_l1 from the records.
 struct E264PacketInfo {
 	int dst_slot, width_mbs, height_mbs;
-	size_t area;           // 0 for a version-4 packet; for a WIRE packet (version 5 or 6, include/edge264_compact.h) the bytes its expansion on the device needs
+	size_t area;           // 0 for a version-4 packet; for a WIRE packet (versions 5 to 7, include/edge264_compact.h) the bytes its expansion on the device needs
 	uint64_t frame_bytes;  // plane_size_Y + plane_size_C the kernels will touch in every slot the packet names
 	uint32_t ref_mask;     // DPB slots its motion refers to
 	bool pred_work;        // it holds inter or PCM macroblocks (else e264_pred_kernel has nothing to do for it)

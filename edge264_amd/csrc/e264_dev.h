@@ -335,8 +335,8 @@ E264_DEV bool open_frame(FrameCtx &f, const E264Job &job)
 		f.mbs = (cmb_t)(pkt + h->mbs_off);
 		f.mbs_g = (const gu8 *)(pkt + h->mbs_off);
 		f.motion = h->motion_off ? (const gu8 *)(pkt + h->motion_off) : nullptr;
-	} else if (h->version - 5u <= 1u && job.expand) {
-		// a wire packet (version 5 or 6, include/edge264_compact.h): records and motion section are where e264_expand_kernel has put them, the rest where it lies
+	} else if (h->version - 5u <= 2u && job.expand) {
+		// a wire packet (version 5, 6 or 7, include/edge264_compact.h): records and motion section are where e264_expand_kernel has put them, the rest where it lies
 		f.mbs = (cmb_t)job.expand;
 		f.mbs_g = (const gu8 *)job.expand;
 		const uint32_t n_compact = *(const uint32_t E264_AS_CONST *)(pkt + h->mbs_off); // E264CompactHdr.n_compact

@@ -11,7 +11,7 @@ struct E264Job {
 	const uint8_t *packet;
 	uint8_t *const *dpb;
 	uint8_t *dbk; // per-stream scratch, E264_SCRATCH_BYTES(macroblocks) (NULL: no deblocking, no intra bitmap -- host tests only, the back end always has one)
-	uint8_t *expand; // per-stream expansion buffer of a WIRE packet (version 5 or 6, include/edge264_compact.h: e264_expand_area_bytes), NULL for a version-4 packet
+	uint8_t *expand; // per-stream expansion buffer of a WIRE packet (versions 5 to 7, include/edge264_compact.h: e264_expand_area_bytes), NULL for a version-4 packet
 };
 #define E264_DBK_BYTES 144 // sixteen 8-byte pieces in the layout of the deblocking kernel's lanes + 16 bytes for the whole macroblock (e264_dbkp.h)
 // The scratch of a stream: the parameter records of n_mbs macroblocks, then the INTRA BITMAP of the picture being decoded: one uint16_t per

@@ -194,7 +194,7 @@ extern "C" const char *e264_kernel_build_flags(void)
 }
 
 // ---------------------------------------------------------------------------------
-// Kernel 0 (only for batches with wire packets): version 5 or 6 -> the record array and motion section of version 4 (e264_expand.h)
+// Kernel 0 (only for batches with wire packets): version 5, 6 or 7 -> the record array and motion section of version 4 (e264_expand.h)
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(XP_NT) void e264_expand_kernel(const E264Job *jobs)
 {

@@ -48,17 +48,17 @@ def load():
 
 
 def _level(compact) -> int:
-    """`compact` of the functions below as the level e264front_set_compact takes: 0 off, 1 version 5, 2 version 6"""
+    """`compact` of the functions below as the level e264front_set_compact takes: 0 off, 1 version 5, 2 version 6, 3 version 7"""
     level = int(compact)
-    if level not in (0, 1, 2):
-        raise FrontError(f"compact={compact!r}: 0, 1 or 2")
+    if level not in (0, 1, 2, 3):
+        raise FrontError(f"compact={compact!r}: 0, 1, 2 or 3")
     return level
 
 
 def capture_packets(stream: bytes, n_threads: int = 0, compact: bool | int = False) -> tuple[list[bytes], int, float]:
     """Parses `stream` (Annex B) with the capture sink.  Returns (command packets in decoding order, output frames the
     decoder handed out, seconds of host time spent parsing + emitting).  compact: pictures with inter macroblocks come in the
-    wire form (include/edge264_compact.h): True or 1 gives version 5, 2 gives version 6."""
+    wire form (include/edge264_compact.h): True or 1 gives version 5, 2 gives version 6, 3 gives version 7."""
     L = load()
     L.e264front_set_sink(1)
     L.e264front_set_compact(_level(compact))

@@ -102,7 +102,7 @@ typedef struct E264Emitter {
 	int (*flush_partial)(struct E264Emitter *, int slot); /* sends the picture-so-far as a packet (edge264_hip_frontend.c) */
 	/* sink */
 	int sink_kind;      /* 0 HIP back end, 1 capture, 2 HIP frames + queued packets (external batcher) */
-	int compact;        /* pictures with inter macroblocks leave in the wire form (include/edge264_compact.h): the level of the fold, 1 or 2; 0 off */
+	int compact;        /* pictures with inter macroblocks leave in the wire form (include/edge264_compact.h): the level of the fold, 1 to 3; 0 off */
 	uint8_t *fold_buf;  /* where such a picture's version-4 packet is assembled before it is folded */
 	size_t fold_cap;
 	void *hip_dev, *hip_stream;

@@ -130,9 +130,10 @@ PUBLIC void e264front_set_download(int on) { g_download = on; }
 PUBLIC void e264front_set_pinned(int on) { g_pkt_pinned = on; }
 /* 1: pictures with inter macroblocks leave in the WIRE form (version 5, include/edge264_compact.h: P_Skip / plain 16x16 macroblocks without residual in 12
  * bytes instead of 40), which the back end unfolds on the device; 2: in its second level (version 6: the plain 16x16 macroblocks WITH residual in 24 bytes
- * too); any other value but 0 counts as 1.  Decoders allocated afterwards.  Also E264_FRONT_COMPACT=1 / =2 in the environment. */
+ * too); 3: in its third (version 7: a run of equal entries of skipped macroblocks as one entry; until that level existed 3 counted as 1, which nothing in
+ * the tree relied on); any other value but 0 counts as 1.  Decoders allocated afterwards.  Also E264_FRONT_COMPACT=1 / =2 / =3 in the environment. */
 static int g_compact = -1;
-PUBLIC void e264front_set_compact(int on) { g_compact = on == 2 ? 2 : on != 0; }
+PUBLIC void e264front_set_compact(int on) { g_compact = on == 2 || on == 3 ? on : on != 0; }
 
 /* the device object of GPU `ordinal` (opened on first use); a decoder is bound to the GPU selected by e264front_set_device at
  * the time of its edge264_alloc -- several GPUs in one process: one decoder population per GPU, SURVEY.md 8(e) */
@@ -537,7 +538,7 @@ PUBLIC Edge264Decoder *edge264_alloc(int n_threads, Edge264LogCb log_cb, void *l
 		return NULL;
 	e->sink_kind = g_sink_kind;
 	const int env_compact = getenv("E264_FRONT_COMPACT") ? atoi(getenv("E264_FRONT_COMPACT")) : 0;
-	e->compact = g_compact >= 0 ? g_compact : env_compact == 2 ? 2 : env_compact != 0;
+	e->compact = g_compact >= 0 ? g_compact : env_compact == 2 || env_compact == 3 ? env_compact : env_compact != 0;
 	e->user_alloc = alloc_cb; e->user_free = free_cb; e->user_arg = alloc_arg;
 	e->flush_partial = e264_flush_partial;
 	if (ON_DEVICE(e)) {

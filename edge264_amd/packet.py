@@ -13,6 +13,7 @@ E264_MAGIC = 0x34363245
 E264_VERSION = 4
 E264_VERSION_COMPACT = 5  # the wire form, include/edge264_compact.h
 E264_VERSION_COMPACT2 = 6  # its second level: one-partition macroblocks with residual folded too
+E264_VERSION_COMPACT3 = 7  # its third level: a run of equal plain entries as one entry
 MAX_SLOTS = 32
 
 MB_ABSENT, MB_I4x4, MB_I8x8, MB_I16x16, MB_PCM, MB_INTER = range(6)
@@ -259,7 +260,7 @@ class Packet:
     """Read-only parsed view of a packet."""
 
     def __init__(self, data: bytes):
-        if len(data) >= 8 and int.from_bytes(bytes(data[0:4]), "little") == E264_MAGIC and int.from_bytes(bytes(data[4:8]), "little") in (E264_VERSION_COMPACT, E264_VERSION_COMPACT2):
+        if len(data) >= 8 and int.from_bytes(bytes(data[0:4]), "little") == E264_MAGIC and int.from_bytes(bytes(data[4:8]), "little") in (E264_VERSION_COMPACT, E264_VERSION_COMPACT2, E264_VERSION_COMPACT3):
             # a wire packet (include/edge264_compact.h) is read as the version-4 packet it stands for: one definition of the expansion, the C one
             from . import backend
             data = backend.packet_expand(bytes(data))

@@ -1,5 +1,5 @@
 """Capture replay: a capture file is a concatenation of command packets (self-describing through
-E264FrameHdr.total_bytes; version 4 or one of the wire forms, versions 5 and 6, which the back end unfolds), each tagged with the decoder it belongs to (E264FrameHdr.stream_id).  `e264_multi --dump-packets`
+E264FrameHdr.total_bytes; version 4 or one of the wire forms, versions 5 to 7, which the back end unfolds), each tagged with the decoder it belongs to (E264FrameHdr.stream_id).  `e264_multi --dump-packets`
 writes one; `Capture` reads it back and `replay()` feeds it to the MI355X back end in file order -- one batch per run of
 packets of distinct streams -- so that kernels can be timed and re-verified on real motion / partition statistics without
 the host entropy decoder in the loop (the reference's own trace output plays that role for its CPU path,

@@ -104,7 +104,7 @@ int  e264hip_submit_batch(E264Device *dev, E264Stream *const *streams, E264Packe
  * all correct decoders, src/edge264.c:161-216). */
 const char *e264hip_build_flags(void);
 int  e264hip_packet_check(const void *packet, size_t bytes);
-/* The WIRE form of a packet (version 5, or version 6 for the second level of the fold; include/edge264_compact.h: fewer bytes over PCIe for pictures full of skipped / plain 16x16 macroblocks -- what the
+/* The WIRE form of a packet (version 5, or versions 6 and 7 for the second and third level of the fold; include/edge264_compact.h: fewer bytes over PCIe for pictures full of skipped / plain 16x16 macroblocks -- what the
  * stream itself spends a run length on, src/edge264_slice.c:1651-1849).  Every host-packet entry point (e264hip_frame_submit, e264hip_submit_batch_host /
  * _pinned, e264hip_packet_upload, e264hip_packet_check) takes either form; a wire packet is unfolded on the device by one more kernel in front of the four
  * (into a buffer of the stream's) and means exactly what its expansion means.  C callers use the inline functions of edge264_compact.h (the front end does);
@@ -115,11 +115,17 @@ int  e264hip_packet_check(const void *packet, size_t bytes);
  *   e264hip_packet_compact2        the fold at `level`: 1 gives version 5 (the bytes of e264hip_packet_compact), 2 gives version 6, in which the inter
  *                                  macroblocks of one partition per list WITH residual are folded too (24 / 32 bytes instead of 40 / 48); any other level
  *                                  gives 0 and an error text.  Opt-in: nothing produces version 6 unless asked to
- *   e264hip_packet_expand          version 5 or 6 -> the canonical version-4 packet; out == NULL: the size needed; 0 on error */
+ *   e264hip_packet_fold_bound      the same for every level of the fold there is
+ *   e264hip_packet_fold            levels 1 and 2 give the bytes of e264hip_packet_compact / _compact2; level 3 gives version 7, in which a run of equal plain
+ *                                  entries in a row (a background of skipped macroblocks) travels as one entry and a bit per further macroblock; any other
+ *                                  level gives 0 and an error text.  Opt-in as well; the expansion is that of the version-6 packet of the same picture
+ *   e264hip_packet_expand          version 5, 6 or 7 -> the canonical version-4 packet; out == NULL: the size needed; 0 on error */
 size_t e264hip_packet_compact_bound(const void *packet, size_t bytes);
 size_t e264hip_packet_compact(const void *packet, size_t bytes, void *out, size_t cap);
 size_t e264hip_packet_compact2_bound(const void *packet, size_t bytes, int level);
 size_t e264hip_packet_compact2(const void *packet, size_t bytes, int level, void *out, size_t cap);
+size_t e264hip_packet_fold_bound(const void *packet, size_t bytes, int level);
+size_t e264hip_packet_fold(const void *packet, size_t bytes, int level, void *out, size_t cap);
 size_t e264hip_packet_expand(const void *packet, size_t bytes, void *out, size_t cap);
 /* Same for packets that still live in HOST memory (the finished frames of many decoders, src/edge264_headers.c:532-568,
  * one per stream): staged through each stream's pinned ring, copied and launched on the device queue without any

@@ -1,9 +1,9 @@
-// tools/sanitize/wire_fuzz.cpp -- CHECKING TOOL, host only: the wire forms of a command packet (include/edge264_compact.h, versions 5 and 6) under
+// tools/sanitize/wire_fuzz.cpp -- CHECKING TOOL, host only: the wire forms of a command packet (include/edge264_compact.h, versions 5, 6 and 7) under
 // AddressSanitizer + UndefinedBehaviorSanitizer, as ONE stand-alone program (nothing is loaded into an interpreter): the validation unit
 // (edge264_amd/csrc/e264_check.cpp), the fold, the host expansion and e264_expand_kernel's source compiled for the host (tests/emu/pred_emu.cpp), every buffer a
 // heap block of exactly the size the back end would give it, so that a read or write past an end is a report.
 //
-// For every version-4 packet of the capture files (tools/make_capture.py writes them; any concatenation of packets will do) and for both levels of the fold:
+// For every version-4 packet of the capture files (tools/make_capture.py writes them; any concatenation of packets will do) and for every level of the fold (1 to 3):
 //   fold -> check -> host expansion == the kernel source's expansion (grids of 256 and 1 threads) -> check of the expansion -> refold == the wire bytes,
 //   then N times: damage 1..4 bytes in front of the payload; whatever e264hip_packet_check still accepts is unfolded both ways (equal bytes again) and its
 //   expansion must pass the check.
@@ -68,17 +68,17 @@ int main(int argc, char **argv)
 		uint8_t *v4 = heap_copy(fh, bytes);
 		off += bytes;
 		if (fh->version != E264_VERSION || e264hip_packet_check(v4, bytes)) { free(v4); continue; } // (wire packets of a capture are skipped: folded here)
-		for (int level = 1; level <= 2; level++) {
-			const size_t cap = e264hip_packet_compact2_bound(v4, bytes, level);
+		for (int level = 1; level <= 3; level++) {
+			const size_t cap = e264hip_packet_fold_bound(v4, bytes, level);
 			uint8_t *tmp = (uint8_t *)malloc(cap);
-			const size_t wb = e264hip_packet_compact2(v4, bytes, level, tmp, cap);
+			const size_t wb = e264hip_packet_fold(v4, bytes, level, tmp, cap);
 			if (!wb) { fprintf(stderr, "fold refused: %s\n", e264hip_last_error()); return 1; }
 			uint8_t *wire = heap_copy(tmp, wb);
 			n_fold++;
 			if (e264hip_packet_check(wire, wb)) { fprintf(stderr, "level %d: the fold of a sound packet is refused: %s\n", level, e264hip_last_error()); return 1; }
 			size_t xb;
 			uint8_t *x = unfold(wire, wb, &xb, "fold");
-			if (e264hip_packet_compact2(x, xb, level, tmp, cap) != wb || memcmp(tmp, wire, wb)) { fprintf(stderr, "level %d: refold differs\n", level); return 1; }
+			if (e264hip_packet_fold(x, xb, level, tmp, cap) != wb || memcmp(tmp, wire, wb)) { fprintf(stderr, "level %d: refold differs\n", level); return 1; }
 			free(x);
 			const uint32_t hi = ((const E264FrameHdr *)wire)->payload_off;
 			for (int k = 0; k < per; k++) {
@@ -100,6 +100,6 @@ int main(int argc, char **argv)
 		}
 		free(v4);
 	}
-	printf("wire_fuzz: %ld folds (levels 1 and 2), %ld damaged packets: %ld refused, %ld accepted and unfolded on exact-size buffers; no finding\n", n_fold, n_damaged, n_refused, n_accepted);
+	printf("wire_fuzz: %ld folds (levels 1 to 3), %ld damaged packets: %ld refused, %ld accepted and unfolded on exact-size buffers; no finding\n", n_fold, n_damaged, n_refused, n_accepted);
 	return n_fold ? 0 : 2;
 }

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/wire_probe.py -- where does a host-packet submission spend its time?  One 1080p fixture, N decoders, the front end's road (page-locked, trusted)
-with version-4 and with wire packets of both levels (versions 5 and 6): wall time per batch, host time inside the submit call, kernel time per launch (events), against resident packets.
+with version-4 and with wire packets of every level (versions 5, 6 and 7): wall time per batch, host time inside the submit call, kernel time per launch (events), against resident packets.
 usage (GPU box): python tools/wire_probe.py [file] [streams]        E264_PROBE_LEGS=pinned_v4,pinned_wire restricts the alternating legs (to compare with a build
-that has no version 6), E264_PROBE_ROUNDS=n sets how often they alternate"""
+that has no version 6 or 7), E264_PROBE_ROUNDS=n sets how often they alternate"""
 import json
 import os
 import sys
@@ -21,8 +21,9 @@ def main():
     data = open(os.path.join(ROOT, "tests", "golden", "streams", name), "rb").read()
     plain = [bytes(p) for p in front.capture_packets(data)[0]]
     wire = [bytes(p) for p in front.capture_packets(data, compact=True)[0]]
-    want = os.environ.get("E264_PROBE_LEGS", "pinned_v4,pinned_wire,pinned_wire2").split(",")
+    want = os.environ.get("E264_PROBE_LEGS", "pinned_v4,pinned_wire,pinned_wire2,pinned_wire3").split(",")
     wire2 = [bytes(p) for p in front.capture_packets(data, compact=2)[0]] if "pinned_wire2" in want else []
+    wire3 = [bytes(p) for p in front.capture_packets(data, compact=3)[0]] if "pinned_wire3" in want else []
     front.capture_packets(b"", compact=False)
     dev = backend.Device(0)
     h0 = P.Packet(plain[0]).hdr
@@ -65,10 +66,10 @@ def main():
     dpk = [[dev.upload_packet(p) for p in plain] for _ in sts]
     bs = [dev.make_batch(sts, [dpk[k][f] for k in range(n)]) for f in range(len(plain))]
     timed("resident", lambda f: dev.submit_prepared(bs[f], backend.RUN_ALL), len(plain))
-    # one page-locked buffer per stream and picture (what n decoders leave), all three forms resident in host memory at once; the legs ALTERNATE so that a drift of the
+    # one page-locked buffer per stream and picture (what n decoders leave), all the forms resident in host memory at once; the legs ALTERNATE so that a drift of the
     # box shows as a drift of all
     legs = {}
-    for label, pk in (("pinned_v4", plain), ("pinned_wire", wire), ("pinned_wire2", wire2)):
+    for label, pk in (("pinned_v4", plain), ("pinned_wire", wire), ("pinned_wire2", wire2), ("pinned_wire3", wire3)):
         if label not in want:
             continue
         pins = [[dev.pinned_copy(p) for p in pk] for _ in range(n)]
