@@ -26,6 +26,27 @@ class BackendError(RuntimeError):
     pass
 
 
+class PlaneView(C.Structure):  # E264PlaneView of include/edge264_hip.h
+    _fields_ = [("offset", C.c_uint32), ("stride", C.c_uint32), ("width", C.c_uint16), ("height", C.c_uint16)]
+
+
+class View(C.Structure):  # E264View: Y, Cb, Cr
+    _fields_ = [("plane", PlaneView * 3)]
+
+
+DIGEST_MAX_BATCH = 4096
+
+
+def as_view(view) -> View:
+    """a View, or the dict digest.frame_view returns ({"offset": [Y, Cb, Cr], "stride": ..., "width": ..., "height": ...}), as the C structure"""
+    if isinstance(view, View):
+        return view
+    v = View()
+    for p in range(3):
+        v.plane[p] = PlaneView(int(view["offset"][p]), int(view["stride"][p]), int(view["width"][p]), int(view["height"][p]))
+    return v
+
+
 def load_library():
     """Loads libedge264_hip.so (in-tree, built by __graft_entry__.build()).  Fails loudly."""
     global _lib
@@ -80,6 +101,9 @@ def load_library():
         "e264hip_build_flags": (C.c_char_p, []),
         "e264hip_frame_device_ptr": (vp, [vp, i]),
         "e264hip_launch_counts": (i, [vp, C.POINTER(C.c_uint64), i, i]),
+        "e264hip_view_check": (i, [C.POINTER(View), sz]),
+        "e264hip_frame_digest": (i, [vp, i, C.POINTER(View), C.POINTER(C.c_uint64)]),
+        "e264hip_digest_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -104,7 +128,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_packet_buffer", "e264hip_frame_wait", "e264hip_frame_download", "e264hip_packet_upload",
     "e264hip_packet_free", "e264hip_packet_check", "e264hip_packet_compact_bound", "e264hip_packet_compact", "e264hip_packet_compact2_bound", "e264hip_packet_compact2", "e264hip_packet_fold_bound", "e264hip_packet_fold", "e264hip_packet_expand", "e264hip_submit_batch", "e264hip_submit_batch_host", "e264hip_submit_batch_pinned", "e264hip_host_alloc", "e264hip_host_free", "e264hip_batch_create", "e264hip_batch_submit", "e264hip_batch_free", "e264hip_event_record", "e264hip_event_elapsed_ms", "e264hip_event_query",
     "e264hip_kernel_timing", "e264hip_kernel_time_ms", "e264hip_set_option", "e264hip_build_flags", "e264hip_frame_device_ptr",
-    "e264hip_launch_counts",
+    "e264hip_launch_counts", "e264hip_view_check", "e264hip_frame_digest", "e264hip_digest_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -165,6 +189,11 @@ def packet_expand(pkt: bytes) -> bytes:
     if not n:
         raise BackendError(f"packet_expand: {last_error()}")
     return bytes(out[:n])
+
+
+def view_check(view, slot_bytes: int) -> int:
+    """Host-only validation of a picture's view against a slot of slot_bytes (no GPU needed): 0 or an errno value."""
+    return load_library().e264hip_view_check(C.byref(as_view(view)), slot_bytes)
 
 
 def last_error() -> str:
@@ -262,6 +291,19 @@ class Device:
     def free_batch(self, batch) -> None:
         self.L.e264hip_batch_free(batch)
 
+    def digest_batch(self, streams, slots, views) -> np.ndarray:
+        """The digests (include/edge264_hip.h, version 1) of views[k] of slot slots[k] of streams[k], computed on the device behind everything
+        queued on the streams' lane: an (n, 3) uint64 array, Y / Cb / Cr per row, in call order.  Blocks."""
+        n = len(streams)
+        if not (len(slots) == len(views) == n):
+            raise ValueError("digest_batch: streams, slots and views differ in length")
+        out = np.zeros((n, 3), np.uint64)
+        sa = (C.c_void_p * max(n, 1))(*[s.h for s in streams])
+        la = (C.c_int * max(n, 1))(*[int(x) for x in slots])
+        va = (View * max(n, 1))(*[as_view(v) for v in views])
+        _check(self.L, self.L.e264hip_digest_batch(self.h, sa, la, va, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "digest_batch")
+        return out
+
     def event_record(self, idx: int) -> None:
         _check(self.L, self.L.e264hip_event_record(self.h, idx), "event_record")
 
@@ -342,6 +384,16 @@ class Stream:
         out = np.empty(self.frame_bytes, np.uint8)
         _check(self.L, self.L.e264hip_frame_download(self.h, slot, out.ctypes.data, out.nbytes), "frame_download")
         return out
+
+    def digest(self, slot: int, view=None):
+        """(Y, Cb, Cr) digests of the picture in `slot`, computed on the device behind everything queued for the stream (a submission, a fill): three
+        ints.  view: where the picture lies (digest.frame_view; a backend.View); default the whole picture in the reference's layout.  Blocks."""
+        if view is None:
+            from .digest import frame_view
+            view = frame_view(self.w, self.h_mbs)
+        out = (C.c_uint64 * 3)()
+        _check(self.L, self.L.e264hip_frame_digest(self.h, slot, C.byref(as_view(view)), out), "frame_digest")
+        return tuple(int(x) for x in out)
 
     def flush(self) -> None:
         _check(self.L, self.L.e264hip_stream_flush(self.h), "stream_flush")

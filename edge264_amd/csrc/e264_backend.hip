@@ -764,6 +764,62 @@ API int e264hip_frame_download(E264Stream *s, int slot, void *dst, size_t bytes)
 	return 0;
 }
 
+// Digests of n pictures (include/edge264_hip.h), one kernel on the streams' lane behind everything queued there.  The job table goes up and the results
+// come down through ONE page-locked block [jobs | results] and one device block of the same shape, both from the recycler and back in it after the wait
+// (sized for n rounded up to 64, so that calls of similar size find each other's blocks).  On the lane, under dev->lock: the table's copy, the clear of the
+// results (the workgroups ADD to them), the kernel, the results' copy, and the call's own serial -- a lane mark as a fill takes, so that a slot freed while the
+// kernel runs is parked behind it.  The wait is for that serial's event, outside the lock.
+// The slots' pointers and sizes are read before that lock is taken and without batch_lock: the caller drives these streams, as for a submission (a frame_free of
+// another thread between the checks and the launch would still leave the block alive -- parked behind a later mark -- but the picture in it is no longer the caller's).
+API int e264hip_digest_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, uint64_t *out)
+{
+	if (!dev || n < 0 || n > E264_DIGEST_MAX_BATCH) return fail(EINVAL, "digest_batch: null device or n outside 0..4096");
+	if (n == 0) return 0;
+	if (!streams || !slots || !views || !out) return fail(EINVAL, "digest_batch: null argument");
+	int r;
+	for (int i = 0; i < n; i++) {
+		if ((r = check_lane(dev, streams, i))) return r;
+		if (slots[i] < 0 || slots[i] >= E264_MAX_SLOTS || !streams[i]->h_table[slots[i]]) return fail(EINVAL, "digest_batch: slot out of range or not allocated");
+		if ((r = e264hip_view_check(&views[i], streams[i]->slot_bytes[slots[i]]))) return r;
+	}
+	if (set_device(dev)) return EIO;
+	const int lane = streams[0]->lane;
+	const size_t cap = ((size_t)n + 63) & ~(size_t)63, jobs_bytes = cap * sizeof(E264DigestJob), bytes = jobs_bytes + cap * 3 * sizeof(uint64_t);
+	uint8_t *h = (uint8_t *)mem_acquire(dev, bytes, true), *d = h ? (uint8_t *)mem_acquire(dev, bytes, false) : nullptr;
+	if (!d) { mem_release(dev, h, bytes, true, 0, 0); return fail(ENOMEM, "digest_batch: job table"); }
+	E264DigestJob *jobs = (E264DigestJob *)h;
+	uint32_t max_chunks = 1;
+	for (int i = 0; i < n; i++) {
+		jobs[i].base = streams[i]->h_table[slots[i]];
+		jobs[i].slot_bytes = streams[i]->slot_bytes[slots[i]];
+		jobs[i].view = views[i];
+		jobs[i].chunks = e264_digest_chunks(&views[i]);
+		max_chunks = std::max(max_chunks, jobs[i].chunks);
+	}
+	uint64_t serial;
+	hipError_t e;
+	{
+		std::lock_guard<std::mutex> g(dev->lock);
+		hipStream_t q = dev->q[lane];
+		e = hipMemcpyAsync(d, h, (size_t)n * sizeof(E264DigestJob), hipMemcpyHostToDevice, q);
+		if (e == hipSuccess) e = hipMemsetAsync(d + jobs_bytes, 0, (size_t)n * 3 * sizeof(uint64_t), q);
+		if (e == hipSuccess) e = e264_launch_digest((const E264DigestJob *)d, n, max_chunks, (uint64_t *)(d + jobs_bytes), q);
+		if (e == hipSuccess) e = hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, (size_t)n * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, q);
+		serial = next_serial(dev, lane); // (also after an error: whatever was queued reads the two blocks until the lane has passed this point)
+	}
+	r = e == hipSuccess ? serial_wait(dev, serial, lane) : fail(EIO, "digest_batch", e);
+	if (!r) memcpy(out, h + jobs_bytes, (size_t)n * 3 * sizeof(uint64_t));
+	mem_release(dev, h, bytes, true, serial, lane);
+	mem_release(dev, d, bytes, false, serial, lane);
+	return r;
+}
+
+API int e264hip_frame_digest(E264Stream *s, int slot, const E264View *view, uint64_t out[3])
+{
+	if (!s) return fail(EINVAL, "frame_digest: null stream");
+	return e264hip_digest_batch(s->dev, &s, &slot, view, 1, out);
+}
+
 API int e264hip_packet_upload(E264Device *dev, const void *packet, size_t bytes, E264Packet **out)
 {
 	if (!dev || !out) return fail(EINVAL, "null argument");

@@ -205,6 +205,22 @@ API int e264hip_packet_check(const void *packet, size_t bytes)
 	return r ? r : e264_check_records(packet, {nullptr, nullptr}, &info);
 }
 
+// Where a picture's samples lie in a slot of slot_bytes (E264View, include/edge264_hip.h): what the digest kernel may read.  Every sum in 64 bits:
+// offset and stride are 32-bit and height 16-bit, so offset + (height - 1) * stride + width stays below 2^49 and cannot wrap.
+API int e264hip_view_check(const E264View *v, size_t slot_bytes)
+{
+	static const char *const names[3] = {"Y", "Cb", "Cr"};
+	if (!v) return fail(EINVAL, "view_check: null view");
+	for (int p = 0; p < 3; p++) {
+		const E264PlaneView &pl = v->plane[p];
+		if (pl.width < 1 || pl.height < 1) return fail(EINVAL, "view_check: a plane without samples", names[p]);
+		if (pl.stride < pl.width) return fail(EINVAL, "view_check: stride below width", names[p]);
+		const uint64_t end = (uint64_t)pl.offset + (uint64_t)(pl.height - 1u) * pl.stride + pl.width;
+		if (end > (uint64_t)slot_bytes) return fail(EINVAL, "view_check: the plane leaves the slot", names[p]);
+	}
+	return 0;
+}
+
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.
 // e264hip_packet_fold takes every level; _compact2 keeps what it took when it was written (1 and 2), _compact is level 1.
 API size_t e264hip_packet_fold_bound(const void *packet, size_t bytes, int level)

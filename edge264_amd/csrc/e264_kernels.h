@@ -36,4 +36,17 @@ extern "C" hipError_t e264_launch_frames(const E264Job *jobs, int n_jobs, int ma
 // e264_expand_kernel alone (a batch's wire packets, on the queue of its upload); E264Plan.expand runs it in front of the four instead
 extern "C" hipError_t e264_launch_expand(const E264Job *jobs, int n_jobs, int max_mbs, hipStream_t stream);
 
+// e264_digest_kernel (e264_digest.h, e264_digest.hip: a translation unit of its own).  One job = one picture to digest: the slot, its size -- the kernel reads no
+// byte outside [base, base + slot_bytes) -- and where the samples lie in it (a view e264hip_view_check has accepted for slot_bytes).  base is 16-byte aligned
+// (a device allocation).  chunks = e264_digest_chunks(view): the workgroups the picture gets.
+struct E264DigestJob {
+	const uint8_t *base;
+	uint64_t slot_bytes;
+	E264View view;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_digest_chunks(const E264View *view);
+// out[3 i + p] += the digest of plane p of job i: the caller clears out (3 n_jobs values) on `stream` in front.  max_chunks: the largest chunks among the jobs.
+extern "C" hipError_t e264_launch_digest(const E264DigestJob *jobs, int n_jobs, uint32_t max_chunks, uint64_t *out, hipStream_t stream);
+
 #endif

@@ -11,13 +11,16 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
 // --out writes s<k>.yuv (cropped Y, Cb, Cr planes of every output frame, as README.md:126-155 of the reference
 // does); --dump-packets appends every command packet (self-describing: E264FrameHdr.total_bytes) = the capture
-// format of SURVEY.md 8(f) rank 2.  Prints one JSON line with the throughput.
+// format of SURVEY.md 8(f) rank 2.  --digest writes s<k>.digest: one line per output frame and view, the three 16-digit hex values of the
+// picture's digest (include/edge264_hip.h, version 1: Y, Cb, Cr), computed on the device where the picture lies -- it works with --no-download, whose
+// pictures nothing else verifies.  A VERIFICATION mode: every frame's digest is a blocking call, and frames are fetched only when the decoder's
+// queued packets have left for the device (as with read-back), so its frame rate is not the product's.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -66,6 +69,7 @@ struct Front {
 	void *(*stream)(void *);
 	void *(*device)(void);
 	void *(*device_of)(void *);
+	int (*frame_digest)(void *, const Edge264Frame *, int, uint64_t *); // (bound with --digest only)
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -91,6 +95,7 @@ struct Stream {
 	const uint8_t *first_nal = nullptr;
 	long frames = 0;
 	FILE *out = nullptr;
+	FILE *dig = nullptr;   // --digest: s<k>.digest
 	struct Pkt { void *data; size_t bytes; };
 	std::deque<Pkt> q;     // parsed, not yet submitted (guarded by the queue mutex)
 	std::atomic<bool> finished{false}; // its worker will queue nothing more (read outside `mu` by the other workers)
@@ -125,7 +130,7 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir;
 	std::vector<int> devices; // --devices
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
 	int device = 0, repeat = 1, n_threads = 1, loops = 1; // --loops K: every stream is played K times back to back (steady state)
@@ -154,13 +159,17 @@ int main(int argc, char **argv)
 		else if (a == "--pin") pin = true;
 		else if (a == "--stay") stay = true;
 		else if (a == "--out") out_dir = next();
+		else if (a == "--digest") digest_dir = next();
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--dump-packets FILE] a.264 ...\n");
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--dump-packets FILE] a.264 ...\n"
+			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
+			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n");
 		return 2;
 	}
+	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -173,6 +182,26 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
+	F.frame_digest = nullptr;
+	if (!digest_dir.empty()) { // e264front_frame_digest lives in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
+		const size_t slash = front_path.rfind('/');
+		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
+		void *dl = dlopen(dpath.c_str(), RTLD_NOW | RTLD_LOCAL);
+		char exe[4096];
+		const ssize_t n = dl ? 0 : readlink("/proc/self/exe", exe, sizeof(exe) - 1);
+		if (!dl && n > 0) {
+			exe[n] = 0;
+			dpath = std::string(exe);
+			dpath = dpath.substr(0, dpath.rfind('/')) + "/libedge264_frontdigest.so";
+			dl = dlopen(dpath.c_str(), RTLD_NOW | RTLD_LOCAL);
+		}
+		if (!dl) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; }
+		bind(dl, "e264front_frame_digest", F.frame_digest);
+		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
+		int (*use)(void *, void *) = nullptr;
+		bind(dl, "e264front_digest_use", use);
+		if (use(fl, hl)) { fprintf(stderr, "e264_multi: e264front_digest_use failed\n"); return 2; }
+	}
 	if (!parse_only) {
 	bind(hl, "e264hip_submit_batch_host", H.submit_batch_host); bind(hl, "e264hip_device_sync", H.device_sync);
 	bind(hl, "e264hip_submit_batch_pinned", H.submit_batch_pinned); bind(hl, "e264hip_event_record", H.event_record); bind(hl, "e264hip_event_query", H.event_query);
@@ -208,6 +237,11 @@ int main(int argc, char **argv)
 				t.out = fopen(o.c_str(), "wb");
 				if (!t.out) { perror(o.c_str()); return 2; }
 			}
+			if (!digest_dir.empty()) {
+				std::string o = digest_dir + "/s" + std::to_string(S.size() - 1) + ".digest";
+				t.dig = fopen(o.c_str(), "w");
+				if (!t.dig) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -223,6 +257,14 @@ int main(int argc, char **argv)
 		while (F.get_frame(s.dec, &fr, 0) == 0) {
 			s.frames++; n++;
 			if (s.out) write_frame(s.out, fr);
+			if (s.dig)
+				for (int v = 0; v < 2; v++) { // MVC: the second view's line follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					uint64_t d[3];
+					const int r = F.frame_digest(s.dec, &fr, v, d);
+					if (r) { fprintf(stderr, "e264front_frame_digest: %d (%s)\n", r, H.last_error()); _exit(1); }
+					fprintf(s.dig, "%016llx %016llx %016llx\n", (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2]);
+				}
 		}
 		return n;
 	};
@@ -241,7 +283,8 @@ int main(int argc, char **argv)
 	//    cannot go on right now -- it is `ahead` pictures ahead, or it must hand out frames (ENOBUFS, edge264.h) while some of its
 	//    pictures are still only queued -- reports BLOCKED and its thread turns to its next decoder (round 3; before, the thread
 	//    slept until the next batch had taken the decoder's packet, with its other decoders idle)
-	const bool must_submit_before_fetch = !parse_only && !no_download;
+	// (--digest reads the picture on the device as read-back does: its packet must be there before the digest is queued)
+	const bool must_submit_before_fetch = !parse_only && (!no_download || !digest_dir.empty());
 	enum Adv { GOT, ENDED, BLOCKED };
 	auto advance = [&](Stream &s) -> Adv {
 		{
@@ -456,6 +499,7 @@ int main(int argc, char **argv)
 		drain(s);
 		total_frames += s.frames;
 		if (s.out) fclose(s.out);
+		if (s.dig) fclose(s.dig);
 		F.free_dec(&s.dec);
 	}
 	if (dump) fclose(dump);

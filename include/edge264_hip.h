@@ -84,6 +84,42 @@ void *e264hip_frame_device_ptr(E264Stream *s, int slot);
  * recycled by the device object instead of hipFree'd, which would drain every queue.) */
 int  e264hip_stream_flush(E264Stream *s);
 
+/* ---- digests of decoded pictures, computed on the device ------------------------------------------------ */
+/* Verifying a picture without reading it back (e264hip_frame_download moves the whole padded slot, 3.1 MB at 1080p): the device
+ * reads the picture's samples where they lie and hands out three 64-bit numbers.  The reference has no counterpart (a test of it
+ * hashes Edge264Frame's planes on the host, which include/edge264_digest.h's e264_digest_plane does in the same arithmetic).
+ *
+ * THE DIGEST, version E264_DIGEST_VERSION.  For one plane of w x h samples s[y][x], with i = y * w + x:
+ *     fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16      (mod 2^32)
+ *     K(i) = fmix32(i) | 1
+ *     D    = sum over i of (s_i + 1) * K(i)                                                       (mod 2^64)
+ * A picture's digest is three such values: Y, Cb, Cr, each plane indexed from 0 over its own (cropped) view, row-major.  The sum
+ * commutes, so every split over lanes, waves and workgroups gives the same bits; one changed sample changes D (an odd K times a
+ * difference below 256 is not 0 mod 2^64); the + 1 makes a plane of zeros depend on its size.  It is NOT cryptographic: it
+ * detects decoding errors, not an adversary.
+ *
+ * WHERE A PICTURE LIES.  E264View is what an Edge264Frame says about a slot: plane pointers minus the slot's base, strides,
+ * cropped widths and heights -- cropping, padded layouts and the second MVC view are all just other numbers.
+ * e264hip_view_check (host only, like e264hip_packet_check: 0 or EINVAL with a text) accepts a view only if every plane has
+ * width >= 1, height >= 1, stride >= width and offset + (height - 1) * stride + width <= slot_bytes, computed in 64 bits. */
+typedef struct { uint32_t offset, stride; uint16_t width, height; } E264PlaneView; /* bytes from the slot's start; bytes between rows; samples */
+typedef struct { E264PlaneView plane[3]; } E264View;                               /* Y, Cb, Cr */
+#define E264_DIGEST_VERSION 1
+int  e264hip_view_check(const E264View *v, size_t slot_bytes);
+/* out[3 i .. 3 i + 2] = the digest of views[i] of slot slots[i] of streams[i]; e264hip_frame_digest is the batch of one.  Both
+ * BLOCK until `out` (ordinary host memory) is filled.
+ * Ordering: one kernel, queued on the streams' compute lane behind everything queued there -- a digest asked for right after
+ *   e264hip_frame_submit, e264hip_submit_batch* or e264hip_frame_fill, with no wait between, sees that work's result.  All streams
+ *   of a call belong to `dev` and share one lane, as for a submission (else EINVAL); a stream may appear more than once (the pass
+ *   only reads).  The call waits for its own event, never for the device.
+ * Lifetime: the call marks the lane as a fill does, so a slot freed while it runs stays parked behind it (e264hip_frame_free never
+ *   hands memory back under a kernel); the caller drives the streams, as for a submission.
+ * Errors: EINVAL (and nothing is queued) for a null pointer, n < 0, n > E264_DIGEST_MAX_BATCH, a slot out of range or not
+ *   allocated, a view e264hip_view_check refuses for that slot's size; e264hip_last_error() names the cause.  n == 0 returns 0. */
+#define E264_DIGEST_MAX_BATCH 4096
+int  e264hip_frame_digest(E264Stream *s, int slot, const E264View *view, uint64_t out[3]);
+int  e264hip_digest_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, uint64_t *out);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
