@@ -150,7 +150,8 @@ class StreamSynth:
                  filter_offsets=(0, 0), deblock_idc: int = 0, n_slots: int = 6,
                  weight_denoms=None, weight_range=(-32, 96), offset_range=(-20, 20), weight_pins: float = 0.0,
                  scaling_range=(8, 40), level_ends: bool = False, mv_ends: float = 0.0, chroma_qp_offsets=None,
-                 place=None, partitions=None, mv_classes=None, both_lists: bool = False, coded_all: bool = False):
+                 place=None, partitions=None, mv_classes=None, both_lists: bool = False, coded_all: bool = False,
+                 pcm_samples=None, level_hook=None):
         """The range-end options:
         weight_denoms      (luma, chroma) log2 weight denominator pairs, one drawn per explicitly weighted slice (default: each of 3..6)
         weight_range       explicit weights drawn from [lo, hi]; offset_range: explicit offsets from [lo, hi]
@@ -171,7 +172,12 @@ class StreamSynth:
                            part stays within the range the vector is drawn from (mv_range); mv_ends does not apply
         both_lists         every quadrant of a B macroblock predicts from both lists
         coded_all          every inter macroblock carries chroma DC and all 16 + 8 4x4 blocks; with t8x8 (and not partitions="4x4") all of
-                           them have the 8x8 transform and carry its four blocks"""
+                           them have the 8x8 transform and carry its four blocks
+        The content options (what the samples are, where the draws above only decide the syntax):
+        pcm_samples        function (frame_no, mbx, mby) -> the 384 bytes (256 Y, 64 Cb, 64 Cr) of an I_PCM macroblock, instead of 384 drawn ones
+        level_hook         function (what, qp) -> int16 levels in the reference's transposed order, or None for the usual draw; asked for every
+                           block of levels, what one of "luma_dc" (16), "chroma_dc" (16, the first 8 used), "luma8x8" (64), "luma4x4" (16),
+                           "ac" (16: the blocks of an Intra16x16 macroblock and of chroma, whose first level is then cleared)"""
         self.w, self.h = width_mbs, height_mbs
         self.rng = np.random.default_rng(seed)
         self.t8x8, self.scaling, self.weighted, self.deblock = t8x8, scaling, weighted, deblock
@@ -191,6 +197,7 @@ class StreamSynth:
         assert partitions in (None, "4x4") and all(0 <= c <= 5 for c in (mv_classes or ()))
         self.place, self.partitions, self.both_lists, self.coded_all = place, partitions, both_lists, coded_all
         self.mv_classes = tuple(mv_classes) if mv_classes else None
+        self.pcm_samples, self.level_hook = pcm_samples, level_hook
         if chroma_qp_offsets is not None:
             self.cqp_off = (int(chroma_qp_offsets[0]), int(chroma_qp_offsets[1]))
         else:
@@ -210,6 +217,10 @@ class StreamSynth:
         rng = self.rng
         c = np.zeros(n, np.int16)
         N = 4 if n == 16 else 8
+        if self.level_hook is not None:
+            got = self.level_hook(self._LEVEL_CALLS[n, maxnz, lowfreq], qp)
+            if got is not None:
+                return np.asarray(got, np.int16).reshape(n).copy()
         if self.lev_mode:
             return self._end_levels(n, N, maxnz, lowfreq)
         if self.stress:
@@ -223,6 +234,8 @@ class StreamSynth:
             c[(x % N) * N + (y % N)] = v if v else 1
         return c
 
+    # what next_frame asks _levels for, by (n, maxnz, lowfreq)
+    _LEVEL_CALLS = {(16, 6, 4): "luma_dc", (16, 4, 4): "chroma_dc", (64, 8, 4): "luma8x8", (16, 6, 3): "luma4x4", (16, 4, 3): "ac"}
     _INT16_ENDS = (32767, -32768, -32767, 16000, -16000, 127, -128, 128, -129)
 
     def _end_levels(self, n: int, N: int, maxnz: int, lowfreq: int) -> np.ndarray:
@@ -342,7 +355,8 @@ class StreamSynth:
                 inter, pcm = placed == "inter", placed == "pcm"
             if pcm:
                 b.set_mb(addr, kind=P.MB_PCM, slice_idx=sidx, qp=(0, chroma_qp(0, self.cqp_off[0]), chroma_qp(0, self.cqp_off[1])),
-                         flags=flags, nz_mask=0xffff, pcm=rng.integers(0, 256, 384, dtype=np.uint8).tobytes())
+                         flags=flags, nz_mask=0xffff, pcm=rng.integers(0, 256, 384, dtype=np.uint8).tobytes() if self.pcm_samples is None
+                         else bytes(self.pcm_samples(self.frame_no, mbx, mby)))
                 continue
             luma_blocks, chroma_blocks, luma_dc, chroma_dc = {}, {}, None, None
             full = inter and self.coded_all

@@ -27,6 +27,58 @@
 
 #define EXPORT __attribute__((visibility("default")))
 
+/* ------------------------------------------------------------------------ */
+/* Event counters: how often the SAMPLES' VALUES take the arithmetic below    */
+/* down a branch or out of its range (tests/content_cases.py,                 */
+/* tests/test_content_census.py).  Each is counted at the line it names.      */
+/* Off by default; counting never changes a picture.  The counters are plain  */
+/* globals: meant for a SINGLE-THREADED caller (the tests), nothing in the    */
+/* product or the benchmark enables them.                                     */
+/* ------------------------------------------------------------------------ */
+#define E264O_EVENTS(X) \
+	/* inter: int16 wrap of sixtapHV's x2, by flow (class 4: xFrac 2 first; class 5: yFrac 2, xFrac odd); visible = the sample differs from 32-bit arithmetic */ \
+	X(hv_wrap_pos_c4) X(hv_wrap_neg_c4) X(hv_wrap_pos_c5) X(hv_wrap_neg_c5) X(hv_wrap_visible) \
+	/* the half-sample values b (horizontal) and h (vertical) clipped at 255 / 0 */ \
+	X(half_clip_hi_b) X(half_clip_lo_b) X(half_clip_hi_h) X(half_clip_lo_h) \
+	/* weighted prediction: pmaddubsw and adds16 saturated, the final packus clipped */ \
+	X(madd_sat_pos) X(madd_sat_neg) X(adds_sat_pos) X(adds_sat_neg) X(wp_pack_hi) X(wp_pack_lo) \
+	/* residual: 4x4 output beyond int16, int16 wrap of sample + residual, the DC-only value truncated to int16, its add wrapping */ \
+	X(res4_sat_pos) X(res4_sat_neg) X(res4_add_wrap) X(dc4_trunc) X(dc4_add_wrap) \
+	/* 8x8: dequantisation saturated (qP < 36) / wrapped (qP >= 36), a wrap inside the two passes (per block), samples that differ from wide arithmetic */ \
+	X(idct8_dequant_sat) X(idct8_dequant_wrap) X(idct8_wrap) X(idct8_wrap_visible) \
+	/* intra plane prediction clipped */ \
+	X(plane16_clip_hi) X(plane16_clip_lo) X(planec_clip_hi) X(planec_clip_lo) \
+	/* deblocking, luma lines that pass the alpha / beta test: bS < 4 by ap / aq, its clips; bS 4 by its three decisions */ \
+	X(dbk_soft_ap_aq) X(dbk_soft_ap) X(dbk_soft_aq) X(dbk_soft_none) X(dbk_soft_delta_clip) X(dbk_soft_clip255) X(dbk_soft_p1_clip) \
+	X(dbk_hard_both) X(dbk_hard_p) X(dbk_hard_q) X(dbk_hard_not_small) X(dbk_hard_small_none) \
+	/* luma lines with bS > 0 on a threshold: |p0-q0| at alpha-1 / alpha, a beta difference at beta-1 / beta, bS 4 lines at (alpha>>2)+1 / +2 */ \
+	X(dbk_alpha_m1) X(dbk_alpha) X(dbk_beta_m1) X(dbk_beta) X(dbk_small_m1) X(dbk_small) \
+	/* deblocking, chroma lines that pass the test */ \
+	X(dbkc_soft) X(dbkc_soft_delta_clip) X(dbkc_soft_clip255) X(dbkc_hard)
+#define X(n) EV_##n,
+enum { E264O_EVENTS(X) EV_COUNT };
+#undef X
+static int g_ev_on;
+static int64_t g_ev[EV_COUNT];
+#define EV(n) do { if (g_ev_on) g_ev[EV_##n]++; } while (0)
+#define EV_IF(c, n) do { if (g_ev_on && (c)) g_ev[EV_##n]++; } while (0)
+
+EXPORT void e264o_events_enable(int on) { g_ev_on = on != 0; }
+/* copies up to n counters to out (NULL: none), clears all of them if reset; returns how many events there are */
+EXPORT int e264o_events(int64_t *out, int n, int reset)
+{
+	for (int i = 0; out && i < n && i < EV_COUNT; i++) out[i] = g_ev[i];
+	if (reset) memset(g_ev, 0, sizeof(g_ev));
+	return EV_COUNT;
+}
+/* the events' names in counter order, separated by spaces */
+EXPORT const char *e264o_event_names(void)
+{
+#define X(n) #n " "
+	return E264O_EVENTS(X);
+#undef X
+}
+
 static inline int clip3(int lo, int hi, int v) { return v < lo ? lo : v > hi ? hi : v; }
 static inline int clip255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 static inline int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
@@ -69,8 +121,12 @@ static int norm_adjust8x8(int m, int pos)
 static void add_res4x4(uint8_t *dst, int stride, const int *r)
 {
 	for (int y = 0; y < 4; y++)
-		for (int x = 0; x < 4; x++)
+		for (int x = 0; x < 4; x++) {
+			EV_IF(r[y * 4 + x] > 32767, res4_sat_pos);
+			EV_IF(r[y * 4 + x] < -32768, res4_sat_neg);
+			EV_IF(dst[y * stride + x] + sat16(r[y * 4 + x]) > 32767, res4_add_wrap);
 			dst[y * stride + x] = (uint8_t)clip255(w16(dst[y * stride + x] + sat16(r[y * 4 + x])));
+		}
 }
 
 /* add_idct4x4, edge264_residual.c:108-172.  c[] in transposed order c[x*4+y].
@@ -113,15 +169,78 @@ EXPORT void e264o_add_dc4x4(int dc, uint8_t *dst, int stride)
 	int r[16];
 	for (int i = 0; i < 16; i++)
 		r[i] = w16((dc + 32) >> 6); /* set16() truncates to int16 */
+	EV_IF(r[0] != (dc + 32) >> 6, dc4_trunc);
 	for (int y = 0; y < 4; y++)
-		for (int x = 0; x < 4; x++)
+		for (int x = 0; x < 4; x++) {
+			EV_IF(dst[y * stride + x] + r[0] > 32767, dc4_add_wrap);
 			dst[y * stride + x] = (uint8_t)clip255(w16(dst[y * stride + x] + r[0]));
+		}
+}
+
+/* the two passes of add_idct8x8 (edge264_residual.c:249-342) on d[i][j] (vector i, lane j; i = x, j = y before the first pass), leaving
+ * what is added to row i, column j in d[i][j].  wrap: every sum is an int16 vector lane, as in the reference; *wrapped is set if one of
+ * them left int16.  Without wrap the same sums in 32 bits: what the event counters hold the samples against. */
+static inline int lane16(int v, int wrap, int *wrapped)
+{
+	if (!wrap)
+		return v;
+	if (v != (int16_t)v)
+		*wrapped = 1;
+	return (int16_t)v;
+}
+static void idct8_passes(int d[8][8], int wrap, int *wrapped)
+{
+	#define L(v) lane16(v, wrap, wrapped)
+	for (int pass = 0; pass < 2; pass++) {
+		int o[8][8];
+		for (int j = 0; j < 8; j++) {
+			int d0 = d[0][j], d1 = d[1][j], d2 = d[2][j], d3 = d[3][j], d4 = d[4][j], d5 = d[5][j], d6 = d[6][j], d7 = d[7][j];
+			int e0 = L(d0 + d4);
+			int e1 = L(L(d5 - d3) - L((d7 >> 1) + d7));
+			int e2 = L(d0 - d4);
+			int e3 = L(L(d1 + d7) - L((d3 >> 1) + d3));
+			int e4 = L((d2 >> 1) - d6);
+			int e5 = L(L(d7 - d1) + L((d5 >> 1) + d5));
+			int e6 = L((d6 >> 1) + d2);
+			int e7 = L(L(d3 + d5) + L((d1 >> 1) + d1));
+			int f0 = L(e0 + e6);
+			int f1 = L((e7 >> 2) + e1);
+			int f2 = L(e2 + e4);
+			int f3 = L((e5 >> 2) + e3);
+			int f4 = L(e2 - e4);
+			int f5 = L((e3 >> 2) - e5);
+			int f6 = L(e0 - e6);
+			int f7 = L(e7 - (e1 >> 2));
+			o[0][j] = L(f0 + f7);
+			o[1][j] = L(f2 + f5);
+			o[2][j] = L(f4 + f3);
+			o[3][j] = L(f6 + f1);
+			o[4][j] = L(f6 - f1);
+			o[5][j] = L(f4 - f3);
+			o[6][j] = L(f2 - f5);
+			o[7][j] = L(f0 - f7);
+		}
+		if (pass == 0) {
+			/* transpose, +32 on the new vector 0 (residual.c:298) */
+			for (int i = 0; i < 8; i++)
+				for (int j = 0; j < 8; j++)
+					d[j][i] = o[i][j];
+			for (int j = 0; j < 8; j++)
+				d[0][j] = L(d[0][j] + 32);
+		} else {
+			/* vector i is now row i, lane j is column j (residual.c:309-342) */
+			for (int i = 0; i < 8; i++)
+				for (int j = 0; j < 8; j++)
+					d[i][j] = o[i][j] >> 6;
+		}
+	}
+	#undef L
 }
 
 /* add_idct8x8, edge264_residual.c:194-343 (int16 arithmetic with wraparound) */
 EXPORT void e264o_add_idct8x8(const int16_t *c, int qP, const uint8_t *wS, uint8_t *dst, int stride)
 {
-	int16_t d[8][8]; /* d[i][j]: vector i, lane j  (i = x, j = y before the first pass) */
+	int d[8][8]; /* d[i][j]: vector i, lane j  (i = x, j = y before the first pass) */
 	int div = qP / 6, m = qP % 6;
 	for (int i = 0; i < 8; i++) {
 		for (int j = 0; j < 8; j++) {
@@ -130,54 +249,27 @@ EXPORT void e264o_add_idct8x8(const int16_t *c, int qP, const uint8_t *wS, uint8
 			if (div < 6) { /* scale32, residual.c:13-17, 214-235 */
 				int32_t v = (int32_t)c[pos] * LS;
 				d[i][j] = (int16_t)sat16((v + (1 << (5 - div))) >> (6 - div));
+				EV_IF(d[i][j] != (v + (1 << (5 - div))) >> (6 - div), idct8_dequant_sat);
 			} else { /* residual.c:236-247: packs32(c) * (LS << sh) in int16 */
 				d[i][j] = w16((int32_t)c[pos] * (int32_t)w16(LS << (div - 6)));
+				EV_IF(d[i][j] != (int32_t)c[pos] * (LS << (div - 6)), idct8_dequant_wrap);
 			}
 		}
 	}
-	for (int pass = 0; pass < 2; pass++) {
-		int16_t o[8][8];
-		for (int j = 0; j < 8; j++) {
-			int16_t d0 = d[0][j], d1 = d[1][j], d2 = d[2][j], d3 = d[3][j], d4 = d[4][j], d5 = d[5][j], d6 = d[6][j], d7 = d[7][j];
-			int16_t e0 = w16(d0 + d4);
-			int16_t e1 = w16(d5 - d3 - w16((d7 >> 1) + d7));
-			int16_t e2 = w16(d0 - d4);
-			int16_t e3 = w16(d1 + d7 - w16((d3 >> 1) + d3));
-			int16_t e4 = w16((d2 >> 1) - d6);
-			int16_t e5 = w16(d7 - d1 + w16((d5 >> 1) + d5));
-			int16_t e6 = w16((d6 >> 1) + d2);
-			int16_t e7 = w16(d3 + d5 + w16((d1 >> 1) + d1));
-			int16_t f0 = w16(e0 + e6);
-			int16_t f1 = w16((e7 >> 2) + e1);
-			int16_t f2 = w16(e2 + e4);
-			int16_t f3 = w16((e5 >> 2) + e3);
-			int16_t f4 = w16(e2 - e4);
-			int16_t f5 = w16((e3 >> 2) - e5);
-			int16_t f6 = w16(e0 - e6);
-			int16_t f7 = w16(e7 - (e1 >> 2));
-			o[0][j] = w16(f0 + f7);
-			o[1][j] = w16(f2 + f5);
-			o[2][j] = w16(f4 + f3);
-			o[3][j] = w16(f6 + f1);
-			o[4][j] = w16(f6 - f1);
-			o[5][j] = w16(f4 - f3);
-			o[6][j] = w16(f2 - f5);
-			o[7][j] = w16(f0 - f7);
-		}
-		if (pass == 0) {
-			/* transpose, +32 on the new vector 0 (residual.c:298) */
-			for (int i = 0; i < 8; i++)
-				for (int j = 0; j < 8; j++)
-					d[j][i] = o[i][j];
+	int wide[8][8], wrapped = 0, unused = 0;
+	if (g_ev_on)
+		memcpy(wide, d, sizeof(wide));
+	idct8_passes(d, 1, &wrapped);
+	if (g_ev_on && wrapped) {
+		EV(idct8_wrap);
+		idct8_passes(wide, 0, &unused);
+		for (int i = 0; i < 8; i++)
 			for (int j = 0; j < 8; j++)
-				d[0][j] = w16(d[0][j] + 32);
-		} else {
-			/* vector i is now row i, lane j is column j (residual.c:309-342) */
-			for (int i = 0; i < 8; i++)
-				for (int j = 0; j < 8; j++)
-					dst[i * stride + j] = (uint8_t)clip255(w16(dst[i * stride + j] + (o[i][j] >> 6)));
-		}
+				EV_IF(clip255(w16(dst[i * stride + j] + d[i][j])) != clip255(dst[i * stride + j] + wide[i][j]), idct8_wrap_visible);
 	}
+	for (int i = 0; i < 8; i++)
+		for (int j = 0; j < 8; j++)
+			dst[i * stride + j] = (uint8_t)clip255(w16(dst[i * stride + j] + d[i][j]));
 }
 
 /* transform_dc4x4, edge264_residual.c:352-454. in: c[16] levels (c_v[0..3]).
@@ -451,8 +543,11 @@ EXPORT void e264o_intra16x16(uint8_t *p, int stride, int mode)
 		}
 		int a = 16 * (p[15 * stride - 1] + pT[15]), b = (5 * H + 32) >> 6, c = (5 * V + 32) >> 6;
 		int tmp[16][16];
-		for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++)
+		for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) {
 			tmp[y][x] = clip255((a + b * (x - 7) + c * (y - 7) + 16) >> 5);
+			EV_IF((a + b * (x - 7) + c * (y - 7) + 16) >> 5 > 255, plane16_clip_hi);
+			EV_IF((a + b * (x - 7) + c * (y - 7) + 16) >> 5 < 0, plane16_clip_lo);
+		}
 		for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) p[y * stride + x] = (uint8_t)tmp[y][x];
 		} return;
 	}
@@ -494,8 +589,11 @@ EXPORT void e264o_intra_chroma(uint8_t *p, int stride, int mode)
 			V += (i + 1) * (p[(4 + i) * stride - 1] - (i == 3 ? pT[-1] : p[(2 - i) * stride - 1]));
 		}
 		int a = 16 * (p[7 * stride - 1] + pT[7]), b = (34 * H + 32) >> 6, c = (34 * V + 32) >> 6;
-		for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++)
+		for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) {
 			out[y][x] = clip255((a + b * (x - 3) + c * (y - 3) + 16) >> 5);
+			EV_IF((a + b * (x - 3) + c * (y - 3) + 16) >> 5 > 255, planec_clip_hi);
+			EV_IF((a + b * (x - 3) + c * (y - 3) + 16) >> 5 < 0, planec_clip_lo);
+		}
 		} break;
 	}
 	for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) p[y * stride + x] = (uint8_t)out[y][x];
@@ -514,22 +612,31 @@ static inline int tapH(const Plane *r, int x, int y)
 static inline int tapV(const Plane *r, int x, int y)
 { return PX(r, x, y - 2) - 5 * PX(r, x, y - 1) + 20 * PX(r, x, y) + 20 * PX(r, x, y + 1) - 5 * PX(r, x, y + 2) + PX(r, x, y + 3); }
 /* sixtapHV on int16 intermediates with wraparound, inter.c:4-9; then (+32)>>6 packus (shrrpus16, inter.c:14) */
-static inline int centre(const int *t)
-{
+static inline int centre(const int *t, int cls)
+{ /* cls: 4 = called with rows of horizontal sums (xFrac 2), 5 = with columns of vertical sums (yFrac 2, xFrac odd): for the counters only */
 	int16_t af = w16(t[0] + t[5]), be = w16(t[1] + t[4]), cd = w16(t[2] + t[3]);
 	int16_t x1 = w16(af - be);
 	int16_t x2 = w16((x1 >> 2) + w16(cd - be));
 	int16_t x3 = w16((x2 >> 2) + cd);
+	if (g_ev_on) { /* of the sums above only x2 can leave int16: |x1 >> 2| <= 6630, |cd - be| <= 26520 */
+		int wide2 = (x1 >> 2) + (cd - be);
+		if (wide2 > 32767) { if (cls == 4) EV(hv_wrap_pos_c4); else EV(hv_wrap_pos_c5); }
+		if (wide2 < -32768) { if (cls == 4) EV(hv_wrap_neg_c4); else EV(hv_wrap_neg_c5); }
+		EV_IF(clip255(((wide2 >> 2) + cd + 32) >> 6) != clip255(w16(x3 + 32) >> 6), hv_wrap_visible);
+	}
 	return clip255(w16(x3 + 32) >> 6);
 }
 static inline int avg(int a, int b) { return (a + b + 1) >> 1; }
+/* the packus of a half-sample value b (horizontal) / h (vertical) */
+static inline int half_b(int v) { EV_IF(v > 255, half_clip_hi_b); EV_IF(v < 0, half_clip_lo_b); return clip255(v); }
+static inline int half_h(int v) { EV_IF(v > 255, half_clip_hi_h); EV_IF(v < 0, half_clip_lo_h); return clip255(v); }
 
 /* one luma sample at integer position (x,y) + quarter offsets (xF,yF): 8.4.2.2.1 as
  * organised by decode_inter_luma (inter.c:416-968) */
 static int luma_sample(const Plane *r, int x, int y, int xF, int yF)
 {
-	#define B_(xx, yy) clip255((tapH(r, xx, yy) + 16) >> 5)
-	#define H_(xx, yy) clip255((tapV(r, xx, yy) + 16) >> 5)
+	#define B_(xx, yy) half_b((tapH(r, xx, yy) + 16) >> 5)
+	#define H_(xx, yy) half_h((tapV(r, xx, yy) + 16) >> 5)
 	if (yF == 0) {
 		if (xF == 0) return PX(r, x, y);
 		int b = B_(x, y);
@@ -544,12 +651,12 @@ static int luma_sample(const Plane *r, int x, int y, int xF, int yF)
 	int t[6];
 	if (xF == 2) { /* horizontal first then vertical (inter.c:611-646, 779-802, 929-966) */
 		for (int k = 0; k < 6; k++) t[k] = tapH(r, x, y - 2 + k);
-		int j = centre(t);
+		int j = centre(t, 4);
 		return yF == 2 ? j : avg(j, B_(x, y + (yF == 3)));
 	}
 	/* xF odd, yF == 2: vertical first then horizontal (inter.c:559-609, 741-777, 887-927) */
 	for (int k = 0; k < 6; k++) t[k] = tapV(r, x - 2 + k, y);
-	return avg(centre(t), H_(x + (xF == 3), y));
+	return avg(centre(t, 5), H_(x + (xF == 3), y));
 	#undef B_
 	#undef H_
 }
@@ -565,7 +672,13 @@ typedef struct { int w0, w1, o, wd; } Wod;
 static inline int wpred(int q, int p, const Wod *w)
 {
 	int x = sat16(q * (int8_t)w->w0 + p * (int8_t)w->w1); /* pmaddubsw */
+	EV_IF(q * (int8_t)w->w0 + p * (int8_t)w->w1 > 32767, madd_sat_pos);
+	EV_IF(q * (int8_t)w->w0 + p * (int8_t)w->w1 < -32768, madd_sat_neg);
+	EV_IF(x + (int16_t)w->o > 32767, adds_sat_pos);
+	EV_IF(x + (int16_t)w->o < -32768, adds_sat_neg);
 	x = sat16(x + (int16_t)w->o);                         /* adds16 */
+	EV_IF(x >> w->wd > 255, wp_pack_hi);
+	EV_IF(x >> w->wd < 0, wp_pack_lo);
 	return clip255(x >> w->wd);
 }
 
@@ -822,9 +935,32 @@ static void filter_luma_line(uint8_t *q0p, int step, int bS, int alpha, int beta
 {
 	int p0 = q0p[-step], p1 = q0p[-2 * step], p2 = q0p[-3 * step], p3 = q0p[-4 * step];
 	int q0 = q0p[0], q1 = q0p[step], q2 = q0p[2 * step], q3 = q0p[3 * step];
+	/* (alpha or beta 0: the filter is off for the edge, no threshold to sit on) */
+	EV_IF(alpha && abs(p0 - q0) == alpha - 1, dbk_alpha_m1);
+	EV_IF(alpha && abs(p0 - q0) == alpha, dbk_alpha);
+	EV_IF(beta && (abs(p1 - p0) == beta - 1 || abs(q1 - q0) == beta - 1), dbk_beta_m1);
+	EV_IF(beta && (abs(p1 - p0) == beta || abs(q1 - q0) == beta), dbk_beta);
+	EV_IF(alpha && bS == 4 && abs(p0 - q0) == (alpha >> 2) + 1, dbk_small_m1);
+	EV_IF(alpha && bS == 4 && abs(p0 - q0) == (alpha >> 2) + 2, dbk_small);
 	if (!(abs(p0 - q0) < alpha && abs(p1 - p0) < beta && abs(q1 - q0) < beta))
 		return;
 	int ap = abs(p2 - p0), aq = abs(q2 - q0);
+	if (g_ev_on) {
+		int P = ap < beta, Q = aq < beta, small = abs(p0 - q0) < (alpha >> 2) + 2;
+		if (bS < 4) {
+			int tc = tc0 + P + Q, delta = (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3;
+			if (P && Q) EV(dbk_soft_ap_aq); else if (P) EV(dbk_soft_ap); else if (Q) EV(dbk_soft_aq); else EV(dbk_soft_none);
+			EV_IF(delta != clip3(-tc, tc, delta), dbk_soft_delta_clip);
+			delta = clip3(-tc, tc, delta);
+			EV_IF(p0 + delta != clip255(p0 + delta) || q0 - delta != clip255(q0 - delta), dbk_soft_clip255);
+			int cp = (p2 + ((p0 + q0 + 1) >> 1) - 2 * p1) >> 1, cq = (q2 + ((p0 + q0 + 1) >> 1) - 2 * q1) >> 1;
+			EV_IF((P && cp != clip3(-tc0, tc0, cp)) || (Q && cq != clip3(-tc0, tc0, cq)), dbk_soft_p1_clip);
+		} else if (!small) EV(dbk_hard_not_small);
+		else if (P && Q) EV(dbk_hard_both);
+		else if (P) EV(dbk_hard_p);
+		else if (Q) EV(dbk_hard_q);
+		else EV(dbk_hard_small_none);
+	}
 	if (bS < 4) { /* DEBLOCK_LUMA_SOFT deblock.c:95-129 */
 		int tc = tc0 + (ap < beta) + (aq < beta);
 		int delta = clip3(-tc, tc, (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3);
@@ -855,9 +991,13 @@ static void filter_chroma_line(uint8_t *q0p, int step, int bS, int alpha, int be
 	if (bS < 4) { /* DEBLOCK_CHROMA_SOFT deblock.c:130-152 */
 		int tc = tc0 + 1;
 		int delta = clip3(-tc, tc, (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3);
+		EV(dbkc_soft);
+		EV_IF(delta != (((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, dbkc_soft_delta_clip);
+		EV_IF(p0 + delta != clip255(p0 + delta) || q0 - delta != clip255(q0 - delta), dbkc_soft_clip255);
 		q0p[-step] = (uint8_t)clip255(p0 + delta);
 		q0p[0] = (uint8_t)clip255(q0 - delta);
 	} else { /* DEBLOCK_CHROMA_HARD deblock.c:261-276 */
+		EV(dbkc_hard);
 		q0p[-step] = (uint8_t)((2 * p1 + p0 + q1 + 2) >> 2);
 		q0p[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
 	}

@@ -8,6 +8,8 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -49,12 +51,37 @@ class Oracle:
         self.lib.e264_oracle_decode_frame.restype = C.c_int
         self.lib.e264_oracle_frame_bs.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
         self.lib.e264_oracle_frame_bs.restype = C.c_int
+        self.lib.e264o_events_enable.argtypes = [C.c_int]
+        self.lib.e264o_events.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self.lib.e264o_events.restype = C.c_int
 
     def decode_frame(self, pkt: bytes, dpb: list, passes: int = 3) -> None:
         """dpb: list of 32 uint8 numpy arrays (or None); the destination slot is written in place."""
         r = self.lib.e264_oracle_decode_frame(pkt, len(pkt), _dpb_array(dpb), passes)
         if r:
             raise RuntimeError(f"oracle rejected packet ({r})")
+
+    def event_names(self) -> list:
+        """the oracle's event counters by name, in counter order (oracle/e264_oracle.c E264O_EVENTS)"""
+        self.lib.e264o_event_names.restype = C.c_char_p
+        return self.lib.e264o_event_names().decode().split()
+
+    @contextlib.contextmanager
+    def events(self):
+        """Counts, while the block runs, how often the samples took the oracle's arithmetic down each named branch or out of its range:
+        yields a Counter that holds every event's name and, once the block has ended, its count.  Single-threaded callers only (the
+        counters are the library's globals); the pictures are the same with and without."""
+        names = self.event_names()
+        out = (C.c_int64 * len(names))()
+        seen = collections.Counter()
+        self.lib.e264o_events(None, 0, 1)
+        self.lib.e264o_events_enable(1)
+        try:
+            yield seen
+        finally:
+            self.lib.e264o_events_enable(0)
+            assert self.lib.e264o_events(out, len(names), 1) == len(names)
+            seen.update({n: int(v) for n, v in zip(names, out)})
 
     def frame_bs(self, pkt: bytes, n_mbs: int) -> np.ndarray:
         out = np.zeros((n_mbs, 2, 4, 4), np.uint8)

@@ -12,7 +12,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
-from tests import edge_cases
+from tests import content_cases, edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -64,12 +64,28 @@ CASES = [
 @pytest.mark.parametrize("name,gop,w,h,kw", CASES, ids=[c[0] for c in CASES])
 def test_deblock_emu(emu, name, gop, w, h, kw, split):
     g = synth.StreamSynth(w, h, seed=len(name) * 7 + 1, **kw)
-    nb = P.frame_bytes(w, h)
     rng = np.random.default_rng(5)
-    dpb = [rng.integers(0, 256, nb + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
+    dpb = [rng.integers(0, 256, P.frame_bytes(w, h) + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
+    check_stream(emu, g.gop(gop), dpb, w, h, split, name)
+    if name.startswith("static"):  # the variant build has the copy-only path (-DE264_DBK_ZEROSKIP=1): both paths ran there
+        z, f = C.c_long(), C.c_long()
+        emu.e264emu_deblock_step_counts(C.byref(z), C.byref(f), 1)
+        assert f.value > 0 and (z.value > 0) == emu.has_zeroskip, (z.value, f.value)
+
+
+@pytest.mark.parametrize("split", [0, 1, 2], ids=["mixed_waves", "luma_and_chroma_waves", "luma_and_chroma_workgroups"])
+@pytest.mark.parametrize("name,w,h", content_cases.RUNS, ids=content_cases.RUN_IDS)
+def test_content_cases(emu, name, w, h, split):
+    """the pictures of tests/content_cases.py: `smooth` takes the filters through every decision the oracle counts (ramps with small steps, plateaus
+    at 0 and 255 for the filters' own clips); the others put them behind samples that wrapped or saturated in the reconstruction"""
+    check_stream(emu, content_cases.packets(name, w, h), content_cases.start_dpb(w, h), w, h, split, f"{name} {w}x{h}")
+
+
+def check_stream(emu, pkts, dpb, w, h, split, name):
+    """every picture of pkts: the oracle's reconstruction through the parameter kernel's body and the filter kernels' in the form `split` names"""
+    nb = P.frame_bytes(w, h)
     orc = Oracle()
-    for i, ft in enumerate(gop):
-        pkt = g.next_frame(ft)
+    for i, pkt in enumerate(pkts):
         d = int(P.Packet(pkt).hdr["dst_slot"])
         mine = [None if b is None else b.copy() for b in dpb]
         orc.decode_frame(pkt, mine, 1)          # reconstruction only
@@ -81,16 +97,12 @@ def test_deblock_emu(emu, name, gop, w, h, kw, split):
         got_y = mine[d][:sY * h * 16].reshape(h * 16, sY)
         exp_y = dpb[d][:sY * h * 16].reshape(h * 16, sY)
         bad = got_y != exp_y
-        assert not bad.any(), f"{name} frame {i} ({ft}): luma differs at (y, x) {np.argwhere(bad)[:6].tolist()}"
+        assert not bad.any(), f"{name} frame {i}: luma differs at (y, x) {np.argwhere(bad)[:6].tolist()}"
         got_c = mine[d][sY * h * 16:nb].reshape(h * 8, sY)
         exp_c = dpb[d][sY * h * 16:nb].reshape(h * 8, sY)
         badc = got_c != exp_c
-        assert not badc.any(), f"{name} frame {i} ({ft}): chroma differs at (y, x) {np.argwhere(badc)[:6].tolist()}"
+        assert not badc.any(), f"{name} frame {i}: chroma differs at (y, x) {np.argwhere(badc)[:6].tolist()}"
         assert np.array_equal(mine[d][nb:], dpb[d][nb:])
-    if name.startswith("static"):  # the variant build has the copy-only path (-DE264_DBK_ZEROSKIP=1): both paths ran there
-        z, f = C.c_long(), C.c_long()
-        emu.e264emu_deblock_step_counts(C.byref(z), C.byref(f), 1)
-        assert f.value > 0 and (z.value > 0) == emu.has_zeroskip, (z.value, f.value)
 
 
 # ---- the packed edge arithmetic against the standard's formulas (8.7.2.3 / 8.7.2.4), line by line ----------------------

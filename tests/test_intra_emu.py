@@ -11,7 +11,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
-from tests import edge_cases
+from tests import content_cases, edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -81,45 +81,65 @@ def test_intra_emu_vs_oracle(emu, name, bitmap):
     """bitmap: the prediction kernel leaves the intra bitmap in the stream's scratch and the intra kernel skips by it (what a submission does on
     the device); scan: no scratch, every chunk of every row is scanned (the fallback); planes: e264_intra_planes_kernel -- the picture's chroma by one
     workgroup, then its luma by another (the launcher's form for I pictures split off a mixed submission)"""
-    planes = bitmap == "planes"
-    bitmap = bitmap is True
     c = CASES[name]
     w, h = c["w"], c["h"]
-    scratch = np.full(scratch_bytes(w * h), 0xFF if bitmap else 0, np.uint8)  # (stale ones: the kernel must overwrite every entry it reads)
+    scratch = new_scratch(w, h, bitmap)
     for seed in (1, 2, 3):
         g = _synth(w, h, seed * 131 + len(name), c["kw"])
-        nb = P.frame_bytes(w, h)
         rng = np.random.default_rng(seed)
-        dpb = [rng.integers(0, 256, nb + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
-        orc = Oracle()
-        for ft in c["gop"]:
-            pkt = g.next_frame(ft)
-            d = int(P.Packet(pkt).hdr["dst_slot"])
-            mine = [None if b is None else b.copy() for b in dpb]
-            orc.decode_frame(pkt, dpb, 1)  # reconstruction only: prediction kernel + intra kernel
-            if bitmap:
-                scratch[w * h * 144:] = 0x00 if ft == "I" else 0xFF  # stale entries of the picture before, both ways
-                assert emu.e264emu_pred_frame2(pkt, _dpb_array(mine), scratch.ctypes.data) == 0
-                assert emu.e264emu_intra_frame2(pkt, _dpb_array(mine), scratch.ctypes.data) == 0
-                ntx = (w + 15) // 16
-                bm = scratch[w * h * 144:w * h * 144 + 2 * ntx * h].view("<u2").reshape(h, ntx)
-                kinds = P.Packet(pkt).mbs["kind"].reshape(h, w)
-                want = np.isin(kinds, (P.MB_I4x4, P.MB_I8x8, P.MB_I16x16))
-                got_bits = np.array([[bm[y, x >> 4] >> (x & 15) & 1 for x in range(w)] for y in range(h)], bool)
-                assert np.array_equal(got_bits, want), f"{name} frame {ft}: intra bitmap differs"
-            else:
-                assert emu.e264emu_pred_frame(pkt, _dpb_array(mine)) == 0
-                assert (emu.e264emu_intra_frame_planes if planes else emu.e264emu_intra_frame)(pkt, _dpb_array(mine)) == 0
-            sY = w * 16
-            got_y = mine[d][:sY * h * 16].reshape(h * 16, sY)
-            exp_y = dpb[d][:sY * h * 16].reshape(h * 16, sY)
-            bad = got_y != exp_y
-            assert not bad.any(), f"{name} seed {seed} frame {ft}: luma differs at (y, x) {np.argwhere(bad)[:5].tolist()}"
-            got_c = mine[d][sY * h * 16:nb].reshape(h * 8, sY)
-            exp_c = dpb[d][sY * h * 16:nb].reshape(h * 8, sY)
-            badc = got_c != exp_c
-            assert not badc.any(), f"{name} seed {seed} frame {ft}: chroma differs at (y, x) {np.argwhere(badc)[:5].tolist()}"
-            dpb[d][:] = mine[d]  # (identical) keep going from the emulated picture
+        dpb = [rng.integers(0, 256, P.frame_bytes(w, h) + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
+        check_stream(emu, [(ft, g.next_frame(ft)) for ft in c["gop"]], dpb, w, h, scratch, bitmap, f"{name} seed {seed}")
+
+
+CONTENT = [(n, w, h) for n, w, h in content_cases.RUNS if n in ("idct8_wrap", "dc_add_wrap", "smooth")]  # (the cases with intra macroblocks)
+
+
+@pytest.mark.parametrize("bitmap", [False, True, "planes"], ids=["scan", "bitmap", "planes"])
+@pytest.mark.parametrize("name,w,h", CONTENT, ids=[f"{n}_{w}x{h}" for n, w, h in CONTENT])
+def test_content_cases(emu, name, w, h, bitmap):
+    """the pictures of tests/content_cases.py with intra macroblocks: 8x8 blocks whose first butterflies wrap on both sides of qP 36, DC-only residuals
+    beyond int16 over samples of 255 (Intra16x16 and chroma), small steps over smooth ramps"""
+    pics = list(zip(content_cases.pattern_of(name, w, h), content_cases.packets(name, w, h)))
+    check_stream(emu, pics, content_cases.start_dpb(w, h), w, h, new_scratch(w, h, bitmap), bitmap, f"{name} {w}x{h}")
+
+
+def new_scratch(w, h, bitmap):
+    return np.full(scratch_bytes(w * h), 0xFF if bitmap is True else 0, np.uint8)  # (stale ones: the kernel must overwrite every entry it reads)
+
+
+def check_stream(emu, pics, dpb, w, h, scratch, bitmap, name):
+    """pics: (picture type, packet) in decoding order, through the prediction kernel's body and then the intra kernel's in the form `bitmap` names"""
+    planes = bitmap == "planes"
+    bitmap = bitmap is True
+    nb = P.frame_bytes(w, h)
+    orc = Oracle()
+    for ft, pkt in pics:
+        d = int(P.Packet(pkt).hdr["dst_slot"])
+        mine = [None if b is None else b.copy() for b in dpb]
+        orc.decode_frame(pkt, dpb, 1)  # reconstruction only: prediction kernel + intra kernel
+        if bitmap:
+            scratch[w * h * 144:] = 0x00 if ft == "I" else 0xFF  # stale entries of the picture before, both ways
+            assert emu.e264emu_pred_frame2(pkt, _dpb_array(mine), scratch.ctypes.data) == 0
+            assert emu.e264emu_intra_frame2(pkt, _dpb_array(mine), scratch.ctypes.data) == 0
+            ntx = (w + 15) // 16
+            bm = scratch[w * h * 144:w * h * 144 + 2 * ntx * h].view("<u2").reshape(h, ntx)
+            kinds = P.Packet(pkt).mbs["kind"].reshape(h, w)
+            want = np.isin(kinds, (P.MB_I4x4, P.MB_I8x8, P.MB_I16x16))
+            got_bits = np.array([[bm[y, x >> 4] >> (x & 15) & 1 for x in range(w)] for y in range(h)], bool)
+            assert np.array_equal(got_bits, want), f"{name} frame {ft}: intra bitmap differs"
+        else:
+            assert emu.e264emu_pred_frame(pkt, _dpb_array(mine)) == 0
+            assert (emu.e264emu_intra_frame_planes if planes else emu.e264emu_intra_frame)(pkt, _dpb_array(mine)) == 0
+        sY = w * 16
+        got_y = mine[d][:sY * h * 16].reshape(h * 16, sY)
+        exp_y = dpb[d][:sY * h * 16].reshape(h * 16, sY)
+        bad = got_y != exp_y
+        assert not bad.any(), f"{name} frame {ft}: luma differs at (y, x) {np.argwhere(bad)[:5].tolist()}"
+        got_c = mine[d][sY * h * 16:nb].reshape(h * 8, sY)
+        exp_c = dpb[d][sY * h * 16:nb].reshape(h * 8, sY)
+        badc = got_c != exp_c
+        assert not badc.any(), f"{name} frame {ft}: chroma differs at (y, x) {np.argwhere(badc)[:5].tolist()}"
+        dpb[d][:] = mine[d]  # (identical) keep going from the emulated picture
 
 
 def test_check_vectors_through_the_emulated_kernels(emu):

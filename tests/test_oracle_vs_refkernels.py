@@ -10,7 +10,7 @@ import pytest
 
 from edge264_amd import packet as P
 from edge264_amd import synth
-from tests import edge_cases, layouts, split_cases, structure_cases
+from tests import content_cases, edge_cases, layouts, split_cases, structure_cases
 
 W, H = 6, 5
 ALL_I = (P.MB_I8x8, P.MB_I4x4, P.MB_I16x16)
@@ -133,6 +133,17 @@ def test_range_ends(oracle, refkernels, name, pattern, kw, must):
     for seed in range(4):
         run_stream(oracle, refkernels, seed, pattern, kw, seen=seen)
     assert all(seen[k] for k in must), {k: seen[k] for k in must}
+
+
+@pytest.mark.parametrize("name,w,h", content_cases.RUNS, ids=content_cases.RUN_IDS)
+def test_content_cases(oracle, refkernels, name, w, h):
+    """The pictures of tests/content_cases.py, whose sample values take the reference's int16 vectors over their ends (the 2-D six-tap, the 8x8
+    transform, the DC-only add) and its saturating weighted sums to the negative end: the one place where the oracle's model of those wraps is
+    held to the reference's own kernels.  The census of the same decode must hold the case's events."""
+    with oracle.events() as seen:
+        run_stream(oracle, refkernels, content_cases.SEED, content_cases.pattern_of(name, w, h), content_cases.options_of(name), w, h)
+    must = content_cases.BY_NAME[name][3]
+    assert not content_cases.missing(seen, must), content_cases.missing(seen, must)
 
 
 def test_range_ends_wide(oracle, refkernels):

@@ -11,7 +11,7 @@ import pytest
 
 from edge264_amd import packet as P, synth
 from oracle.pyoracle import Oracle, _dpb_array
-from tests import edge_cases
+from tests import content_cases, edge_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -66,28 +66,39 @@ def test_pred_emu_vs_oracle(emu, name):
     w, h = c["w"], c["h"]
     for seed in (1, 2):
         g = synth.StreamSynth(w, h, seed=seed * 77 + len(name), **c["kw"])
-        nb = P.frame_bytes(w, h)
         rng = np.random.default_rng(seed)
-        dpb = [rng.integers(0, 256, nb + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
-        orc = Oracle()
-        for ft in c["gop"]:
-            pkt = g.next_frame(ft)
-            d = int(P.Packet(pkt).hdr["dst_slot"])
-            mine = [None if b is None else b.copy() for b in dpb]
-            before = mine[d].copy()
-            orc.decode_frame(pkt, dpb, 1)  # reconstruction only: what the prediction kernel + intra kernel produce
-            assert emu.e264emu_pred_frame(pkt, _dpb_array(mine)) == 0
-            my, mc = mb_mask(pkt, w, h)
-            sY, sC = w * 16, w * 16
-            got_y = mine[d][:sY * h * 16].reshape(h * 16, sY)
-            exp_y = dpb[d][:sY * h * 16].reshape(h * 16, sY)
-            bad = (got_y != exp_y) & my
-            assert not bad.any(), f"{name} seed {seed} frame {ft}: luma differs at (y, x) {np.argwhere(bad)[:5].tolist()}"
-            got_c = mine[d][sY * h * 16:nb].reshape(h * 8, sC)
-            exp_c = dpb[d][sY * h * 16:nb].reshape(h * 8, sC)
-            mcc = np.concatenate([mc, mc], axis=1)  # a chroma row is [Cb | Cr]
-            badc = (got_c != exp_c) & mcc
-            assert not badc.any(), f"{name} seed {seed} frame {ft}: chroma differs at (y, x) {np.argwhere(badc)[:5].tolist()}"
-            # samples the kernel does not own (intra, absent macroblocks) stay untouched
-            assert np.array_equal(got_y[~my], before[:sY * h * 16].reshape(h * 16, sY)[~my])
-            assert np.array_equal(got_c[~mcc], before[sY * h * 16:nb].reshape(h * 8, sC)[~mcc])
+        dpb = [rng.integers(0, 256, P.frame_bytes(w, h) + 16, dtype=np.uint8) for _ in range(6)] + [None] * 26
+        check_stream(emu, g.gop(c["gop"]), dpb, w, h, f"{name} seed {seed}")
+
+
+@pytest.mark.parametrize("name,w,h", content_cases.RUNS, ids=content_cases.RUN_IDS)
+def test_content_cases(emu, name, w, h):
+    """the pictures of tests/content_cases.py: samples that take the 16-bit lanes of centre6r over their ends (the reference's int16 wrap), DC-only and 8x8
+    residuals that wrap, weighted sums at the negative end of int16 -- in both builds"""
+    check_stream(emu, content_cases.packets(name, w, h), content_cases.start_dpb(w, h), w, h, f"{name} {w}x{h}")
+
+
+def check_stream(emu, pkts, dpb, w, h, name):
+    """every picture of pkts through the prediction kernel's body, from the oracle's pictures before it (dpb: the slots to start from)"""
+    nb = P.frame_bytes(w, h)
+    orc = Oracle()
+    for i, pkt in enumerate(pkts):
+        d = int(P.Packet(pkt).hdr["dst_slot"])
+        mine = [None if b is None else b.copy() for b in dpb]
+        before = mine[d].copy()
+        orc.decode_frame(pkt, dpb, 1)  # reconstruction only: what the prediction kernel + intra kernel produce
+        assert emu.e264emu_pred_frame(pkt, _dpb_array(mine)) == 0
+        my, mc = mb_mask(pkt, w, h)
+        sY, sC = w * 16, w * 16
+        got_y = mine[d][:sY * h * 16].reshape(h * 16, sY)
+        exp_y = dpb[d][:sY * h * 16].reshape(h * 16, sY)
+        bad = (got_y != exp_y) & my
+        assert not bad.any(), f"{name} frame {i}: luma differs at (y, x) {np.argwhere(bad)[:5].tolist()}"
+        got_c = mine[d][sY * h * 16:nb].reshape(h * 8, sC)
+        exp_c = dpb[d][sY * h * 16:nb].reshape(h * 8, sC)
+        mcc = np.concatenate([mc, mc], axis=1)  # a chroma row is [Cb | Cr]
+        badc = (got_c != exp_c) & mcc
+        assert not badc.any(), f"{name} frame {i}: chroma differs at (y, x) {np.argwhere(badc)[:5].tolist()}"
+        # samples the kernel does not own (intra, absent macroblocks) stay untouched
+        assert np.array_equal(got_y[~my], before[:sY * h * 16].reshape(h * 16, sY)[~my])
+        assert np.array_equal(got_c[~mcc], before[sY * h * 16:nb].reshape(h * 8, sC)[~mcc])

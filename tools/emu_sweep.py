@@ -9,6 +9,7 @@ The tests run fixed cases; this is for leaving a few CPU-hours on it.
     python tools/emu_sweep.py [--seeds A:B] [--split 0|1]      prints one line per mismatch and a summary
 """
 import argparse
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -57,6 +58,8 @@ def main():
     pe.e264emu_deblock_frame2.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int]
     a, b = (int(x) for x in args.seeds.split(":"))
     t0, frames, mbs, bad, skipped = time.time(), 0, 0, [], 0
+    counting = contextlib.ExitStack()
+    seen = counting.enter_context(Oracle().events())  # (what the samples made the arithmetic do: tests/test_content_census.py)
     for seed in range(a, b):
         w, h, gop, kw = options(seed)
         try:
@@ -91,6 +94,9 @@ def main():
                 print(f"MISMATCH seed {seed} picture {k} ({ft}) {w}x{h} first offsets {where} options {kw}", flush=True)
                 dpb[dst][:] = dpb[dst]  # (the oracle's picture stays the reference of what follows)
     dt = time.time() - t0
+    counting.close()
+    print("census: " + " ".join(f"{k}={v}" for k, v in seen.items()))
+    print("events no picture of the sweep reached: " + (" ".join(k for k, v in seen.items() if not v) or "none"))
     print(f"emu_sweep seeds {a}:{b} split {args.split}: {frames} pictures, {mbs} macroblocks, {len(bad)} mismatches, {skipped} generator refusals, {dt:.0f} s")
     return 1 if bad else 0
 

@@ -9,6 +9,7 @@ reconstruction pass and after the deblocking pass.  tests/test_oracle_vs_refkern
     python tools/oracle_sweep.py [--seeds A:B]
 """
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -46,6 +47,8 @@ def main():
     a, b = (int(x) for x in args.seeds.split(":"))
     orc, refk = Oracle(), RefKernels()
     t0, pics, bad, refused = time.time(), 0, [], 0
+    counting = contextlib.ExitStack()
+    seen = counting.enter_context(orc.events())  # (what the samples made the arithmetic do: tests/test_content_census.py)
     for seed in range(a, b):
         w, h, gop, kw = options(seed)
         try:
@@ -73,6 +76,9 @@ def main():
                 pics += 1
         except RuntimeError as e:  # the generator's own limits (DPB too small for the drawn GOP)
             refused += 1
+    counting.close()
+    print("census: " + " ".join(f"{k}={v}" for k, v in seen.items()))
+    print("events no picture of the sweep reached: " + (" ".join(k for k, v in seen.items() if not v) or "none"))
     print(f"oracle_sweep seeds {a}:{b}: {pics} pictures, {len(set(bad))} seeds with a mismatch {sorted(set(bad))[:10]}, {refused} generator refusals, {time.time() - t0:.0f} s")
     return 1 if bad else 0
 
