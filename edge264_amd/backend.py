@@ -35,6 +35,8 @@ class View(C.Structure):  # E264View: Y, Cb, Cr
 
 
 DIGEST_MAX_BATCH = 4096
+PREVIEW_MAX_BATCH = 4096
+PREVIEW_MAX_BYTES = 1 << 28
 
 
 def as_view(view) -> View:
@@ -104,6 +106,9 @@ def load_library():
         "e264hip_view_check": (i, [C.POINTER(View), sz]),
         "e264hip_frame_digest": (i, [vp, i, C.POINTER(View), C.POINTER(C.c_uint64)]),
         "e264hip_digest_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, C.POINTER(C.c_uint64)]),
+        "e264hip_preview_bytes": (sz, [C.POINTER(View), i, C.POINTER(C.c_uint16)]),
+        "e264hip_frame_preview": (i, [vp, i, C.POINTER(View), i, vp, sz]),
+        "e264hip_preview_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, i, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -129,6 +134,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_packet_free", "e264hip_packet_check", "e264hip_packet_compact_bound", "e264hip_packet_compact", "e264hip_packet_compact2_bound", "e264hip_packet_compact2", "e264hip_packet_fold_bound", "e264hip_packet_fold", "e264hip_packet_expand", "e264hip_submit_batch", "e264hip_submit_batch_host", "e264hip_submit_batch_pinned", "e264hip_host_alloc", "e264hip_host_free", "e264hip_batch_create", "e264hip_batch_submit", "e264hip_batch_free", "e264hip_event_record", "e264hip_event_elapsed_ms", "e264hip_event_query",
     "e264hip_kernel_timing", "e264hip_kernel_time_ms", "e264hip_set_option", "e264hip_build_flags", "e264hip_frame_device_ptr",
     "e264hip_launch_counts", "e264hip_view_check", "e264hip_frame_digest", "e264hip_digest_batch",
+    "e264hip_preview_bytes", "e264hip_frame_preview", "e264hip_preview_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -142,6 +148,27 @@ def _check(L, r: int, what: str) -> None:
     if r:
         msg = L.e264hip_last_error()
         raise BackendError(f"{what}: {errno.errorcode.get(r, r)} ({(msg or b'').decode()})")
+
+
+def preview_dims(view, k: int):
+    """[(ow, oh)] of Y, Cb, Cr of a view's preview at reduction k, from the library (host only); raises for what has none"""
+    d = (C.c_uint16 * 6)()
+    if not load_library().e264hip_preview_bytes(C.byref(as_view(view)), k, d):
+        raise ValueError("preview: k is 1, 2 or 3 and every plane of the view has samples")
+    return [(int(d[2 * p]), int(d[2 * p + 1])) for p in range(3)]
+
+
+def preview_bytes(view, k: int) -> int:
+    """e264hip_preview_bytes: the bytes of a view's preview at reduction k (Y | Cb | Cr, each plane tight); 0 for what has none.  Host only."""
+    return int(load_library().e264hip_preview_bytes(C.byref(as_view(view)) if view is not None else None, k, None))
+
+
+def _split_preview(buf: np.ndarray, dims):
+    out, at = [], 0
+    for ow, oh in dims:
+        out.append(buf[at:at + ow * oh].reshape(oh, ow))
+        at += ow * oh
+    return out
 
 
 def packet_check(pkt: bytes) -> int:
@@ -304,6 +331,22 @@ class Device:
         _check(self.L, self.L.e264hip_digest_batch(self.h, sa, la, va, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "digest_batch")
         return out
 
+    def preview_batch(self, streams, slots, views, k: int = 3):
+        """The previews (include/edge264_hip.h, version 1: box filter by 1 << k, k = 1, 2, 3) of views[i] of slot slots[i] of streams[i], computed on the
+        device behind everything queued on the streams' lane: a list of [Y, Cb, Cr] 2-D uint8 arrays, in call order.  Blocks."""
+        n = len(streams)
+        if not (len(slots) == len(views) == n):
+            raise ValueError("preview_batch: streams, slots and views differ in length")
+        cv = [as_view(v) for v in views]
+        dims = [preview_dims(v, k) for v in cv]
+        pitch = max([sum(ow * oh for ow, oh in d) for d in dims], default=0)
+        out = np.zeros((n, pitch), np.uint8)
+        sa = (C.c_void_p * max(n, 1))(*[s.h for s in streams])
+        la = (C.c_int * max(n, 1))(*[int(x) for x in slots])
+        va = (View * max(n, 1))(*cv)
+        _check(self.L, self.L.e264hip_preview_batch(self.h, sa, la, va, n, k, out.ctypes.data, pitch), "preview_batch")
+        return [_split_preview(out[j], dims[j]) for j in range(n)]
+
     def event_record(self, idx: int) -> None:
         _check(self.L, self.L.e264hip_event_record(self.h, idx), "event_record")
 
@@ -394,6 +437,18 @@ class Stream:
         out = (C.c_uint64 * 3)()
         _check(self.L, self.L.e264hip_frame_digest(self.h, slot, C.byref(as_view(view)), out), "frame_digest")
         return tuple(int(x) for x in out)
+
+    def preview(self, slot: int, view=None, k: int = 3):
+        """[Y, Cb, Cr] of the picture in `slot` reduced by 1 << k (k = 1, 2, 3) in each direction, computed on the device behind everything queued for the
+        stream: three 2-D uint8 arrays.  view: as for digest; default the whole picture in the reference's layout.  Blocks."""
+        if view is None:
+            from .digest import frame_view
+            view = frame_view(self.w, self.h_mbs)
+        cv = as_view(view)
+        dims = preview_dims(cv, k)
+        out = np.zeros(sum(ow * oh for ow, oh in dims), np.uint8)
+        _check(self.L, self.L.e264hip_frame_preview(self.h, slot, C.byref(cv), k, out.ctypes.data, out.nbytes), "frame_preview")
+        return _split_preview(out, dims)
 
     def flush(self) -> None:
         _check(self.L, self.L.e264hip_stream_flush(self.h), "stream_flush")

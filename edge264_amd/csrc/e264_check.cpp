@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "e264_check.h"
+#include "../../include/edge264_preview.h"
 
 thread_local char e264_err[256];
 int e264_fail(int code, const char *what, const char *detail)
@@ -219,6 +220,21 @@ API int e264hip_view_check(const E264View *v, size_t slot_bytes)
 		if (end > (uint64_t)slot_bytes) return fail(EINVAL, "view_check: the plane leaves the slot", names[p]);
 	}
 	return 0;
+}
+
+// The size of a view's preview at reduction k (include/edge264_hip.h: Y | Cb | Cr, each plane tight) and its planes' sizes; 0 for what has none.
+API size_t e264hip_preview_bytes(const E264View *v, int log2_factor, uint16_t dims[6])
+{
+	size_t bytes = 0;
+	unsigned d[6];
+	if (!v) return 0;
+	for (int p = 0; p < 3; p++) {
+		if (!e264_preview_dims(v->plane[p].width, v->plane[p].height, log2_factor, &d[2 * p], &d[2 * p + 1])) return 0;
+		bytes += (size_t)d[2 * p] * d[2 * p + 1];
+	}
+	if (dims)
+		for (int i = 0; i < 6; i++) dims[i] = (uint16_t)d[i];
+	return bytes;
 }
 
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.

@@ -49,4 +49,18 @@ extern "C" uint32_t e264_digest_chunks(const E264View *view);
 // out[3 i + p] += the digest of plane p of job i: the caller clears out (3 n_jobs values) on `stream` in front.  max_chunks: the largest chunks among the jobs.
 extern "C" hipError_t e264_launch_digest(const E264DigestJob *jobs, int n_jobs, uint32_t max_chunks, uint64_t *out, hipStream_t stream);
 
+// e264_preview_kernel (e264_preview.h, e264_preview.hip: a translation unit of its own).  One job = one picture to reduce by 1 << k (k = 1, 2, 3): the slot and
+// the view as for a digest job -- no byte outside [base, base + slot_bytes) is read -- and dst, where the picture's preview goes (device memory of
+// e264hip_preview_bytes(view, k) bytes: every byte of it is written once, none outside it).  chunks = e264_preview_chunks(view, k).
+struct E264PreviewJob {
+	const uint8_t *base;
+	uint64_t slot_bytes;
+	E264View view;
+	uint8_t *dst;
+	uint32_t k;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_preview_chunks(const E264View *view, int k);
+extern "C" hipError_t e264_launch_preview(const E264PreviewJob *jobs, int n_jobs, uint32_t max_chunks, hipStream_t stream);
+
 #endif

@@ -11,7 +11,7 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--digest DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
@@ -20,7 +20,9 @@
 // format of SURVEY.md 8(f) rank 2.  --digest writes s<k>.digest: one line per output frame and view, the three 16-digit hex values of the
 // picture's digest (include/edge264_hip.h, version 1: Y, Cb, Cr), computed on the device where the picture lies -- it works with --no-download, whose
 // pictures nothing else verifies.  A VERIFICATION mode: every frame's digest is a blocking call, and frames are fetched only when the decoder's
-// queued packets have left for the device (as with read-back), so its frame rate is not the product's.  Prints one JSON line with the throughput.
+// queued packets have left for the device (as with read-back), so its frame rate is not the product's.  --preview writes s<k>.preview: every output frame's, and
+// every view's, reduced preview (include/edge264_hip.h, version 1: Y | Cb | Cr reduced by 1 << K in each direction, K = --preview-log2, default 3), the bytes one
+// after the other, computed on the device as well; bound and ordered like --digest, and both may be given.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -70,6 +72,7 @@ struct Front {
 	void *(*device)(void);
 	void *(*device_of)(void *);
 	int (*frame_digest)(void *, const Edge264Frame *, int, uint64_t *); // (bound with --digest only)
+	int (*frame_preview)(void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --preview only)
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -96,6 +99,7 @@ struct Stream {
 	long frames = 0;
 	FILE *out = nullptr;
 	FILE *dig = nullptr;   // --digest: s<k>.digest
+	FILE *prev = nullptr;  // --preview: s<k>.preview
 	struct Pkt { void *data; size_t bytes; };
 	std::deque<Pkt> q;     // parsed, not yet submitted (guarded by the queue mutex)
 	std::atomic<bool> finished{false}; // its worker will queue nothing more (read outside `mu` by the other workers)
@@ -130,8 +134,9 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path, digest_dir;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir;
 	std::vector<int> devices; // --devices
+	int preview_log2 = 3; // --preview-log2 K: previews are reduced by 1 << K (1, 2 or 3)
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
 	int device = 0, repeat = 1, n_threads = 1, loops = 1; // --loops K: every stream is played K times back to back (steady state)
 	bool no_download = false; // --no-download: output frames stay in HBM (edge264_get_frame does not copy them back)
@@ -160,16 +165,23 @@ int main(int argc, char **argv)
 		else if (a == "--stay") stay = true;
 		else if (a == "--out") out_dir = next();
 		else if (a == "--digest") digest_dir = next();
+		else if (a == "--preview") preview_dir = next();
+		else if (a == "--preview-log2") preview_log2 = atoi(next().c_str());
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--dump-packets FILE] a.264 ...\n"
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--dump-packets FILE] a.264 ...\n"
 			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
-			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n");
+			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n"
+			"  --preview DIR writes DIR/s<k>.preview: every output frame's and view's preview (Y | Cb | Cr reduced by 1 << K, --preview-log2 K = 1, 2 or 3, default 3),\n"
+			"                computed on the device; bound and ordered like --digest\n");
 		return 2;
 	}
 	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
+	if (!preview_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --preview needs the device (not --parse-only)\n"); return 2; }
+	if (preview_log2 < 1 || preview_log2 > 3) { fprintf(stderr, "e264_multi: --preview-log2 is 1, 2 or 3\n"); return 2; }
+	const bool on_device = !digest_dir.empty() || !preview_dir.empty(); // a pass that reads the pictures where they lie
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -182,8 +194,8 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
-	F.frame_digest = nullptr;
-	if (!digest_dir.empty()) { // e264front_frame_digest lives in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
+	F.frame_digest = nullptr; F.frame_preview = nullptr;
+	if (on_device) { // e264front_frame_digest and e264front_frame_preview live in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
 		const size_t slash = front_path.rfind('/');
 		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
 		void *dl = dlopen(dpath.c_str(), RTLD_NOW | RTLD_LOCAL);
@@ -196,7 +208,8 @@ int main(int argc, char **argv)
 			dl = dlopen(dpath.c_str(), RTLD_NOW | RTLD_LOCAL);
 		}
 		if (!dl) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; }
-		bind(dl, "e264front_frame_digest", F.frame_digest);
+		if (!digest_dir.empty()) bind(dl, "e264front_frame_digest", F.frame_digest);
+		if (!preview_dir.empty()) bind(dl, "e264front_frame_preview", F.frame_preview);
 		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
 		int (*use)(void *, void *) = nullptr;
 		bind(dl, "e264front_digest_use", use);
@@ -242,6 +255,11 @@ int main(int argc, char **argv)
 				t.dig = fopen(o.c_str(), "w");
 				if (!t.dig) { perror(o.c_str()); return 2; }
 			}
+			if (!preview_dir.empty()) {
+				std::string o = preview_dir + "/s" + std::to_string(S.size() - 1) + ".preview";
+				t.prev = fopen(o.c_str(), "wb");
+				if (!t.prev) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -265,6 +283,16 @@ int main(int argc, char **argv)
 					if (r) { fprintf(stderr, "e264front_frame_digest: %d (%s)\n", r, H.last_error()); _exit(1); }
 					fprintf(s.dig, "%016llx %016llx %016llx\n", (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2]);
 				}
+			if (s.prev)
+				for (int v = 0; v < 2; v++) { // MVC: the second view's preview follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					const int f = 1 << preview_log2; // (a bound on the preview's size from the frame itself: ceil(w / f) * ceil(h / f) per plane)
+					std::vector<uint8_t> buf((size_t)((fr.width_Y + f - 1) / f) * ((fr.height_Y + f - 1) / f) + 2 * (size_t)((fr.width_C + f - 1) / f) * ((fr.height_C + f - 1) / f));
+					uint16_t dims[6];
+					const int r = F.frame_preview(s.dec, &fr, v, preview_log2, buf.data(), buf.size(), dims);
+					if (r) { fprintf(stderr, "e264front_frame_preview: %d (%s)\n", r, H.last_error()); _exit(1); }
+					fwrite(buf.data(), 1, (size_t)dims[0] * dims[1] + (size_t)dims[2] * dims[3] + (size_t)dims[4] * dims[5], s.prev);
+				}
 		}
 		return n;
 	};
@@ -283,8 +311,8 @@ int main(int argc, char **argv)
 	//    cannot go on right now -- it is `ahead` pictures ahead, or it must hand out frames (ENOBUFS, edge264.h) while some of its
 	//    pictures are still only queued -- reports BLOCKED and its thread turns to its next decoder (round 3; before, the thread
 	//    slept until the next batch had taken the decoder's packet, with its other decoders idle)
-	// (--digest reads the picture on the device as read-back does: its packet must be there before the digest is queued)
-	const bool must_submit_before_fetch = !parse_only && (!no_download || !digest_dir.empty());
+	// (--digest and --preview read the picture on the device as read-back does: its packet must be there before the pass is queued)
+	const bool must_submit_before_fetch = !parse_only && (!no_download || on_device);
 	enum Adv { GOT, ENDED, BLOCKED };
 	auto advance = [&](Stream &s) -> Adv {
 		{
@@ -500,6 +528,7 @@ int main(int argc, char **argv)
 		total_frames += s.frames;
 		if (s.out) fclose(s.out);
 		if (s.dig) fclose(s.dig);
+		if (s.prev) fclose(s.prev);
 		F.free_dec(&s.dec);
 	}
 	if (dump) fclose(dump);

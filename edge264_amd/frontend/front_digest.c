@@ -22,31 +22,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "edge264_hip.h"
+#include "front_bind.h"
 
-#define PUBLIC __attribute__((visibility("default")))
-
-typedef struct Edge264Decoder Edge264Decoder;
-/* edge264.h:45-62 (layout restated, as edge264_amd/driver/e264_multi.cpp does; the header itself is not part of this repository) */
-typedef struct Edge264Frame {
-	const uint8_t *samples[3];
-	const uint8_t *samples_mvc[3];
-	const uint8_t *mb_errors;
-	int8_t bit_depth_Y, bit_depth_C;
-	int16_t width_Y, width_C, height_Y, height_C, stride_Y, stride_C, stride_mb;
-	int32_t FrameId, FrameId_mvc;
-	int16_t frame_crop_offsets[4];
-	void *return_arg;
-} Edge264Frame;
-
-static struct {
-	int err; /* 0 once everything below is bound */
-	void *(*stream)(Edge264Decoder *);
-	void *(*device_samples)(Edge264Decoder *, const void *);
-	int (*slot_of)(Edge264Decoder *, const void *);
-	void *(*frame_device_ptr)(E264Stream *, int);
-	int (*frame_digest)(E264Stream *, int, const E264View *, uint64_t *);
-} g = {ENODEV, NULL, NULL, NULL, NULL, NULL};
+struct E264FrontBind e264front_bind = {ENODEV, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+#define g e264front_bind
 static pthread_once_t g_once = PTHREAD_ONCE_INIT;
 
 /* the library `name` that lies beside this one */
@@ -77,12 +56,20 @@ static void bind_all(void)
 	*(void **)&g.slot_of = dlsym(fl, "e264front_slot_of");
 	*(void **)&g.frame_device_ptr = dlsym(hl, "e264hip_frame_device_ptr");
 	*(void **)&g.frame_digest = dlsym(hl, "e264hip_frame_digest");
-	if (g.stream && g.device_samples && g.slot_of && g.frame_device_ptr && g.frame_digest) g.err = 0;
+	*(void **)&g.preview_bytes = dlsym(hl, "e264hip_preview_bytes");
+	*(void **)&g.frame_preview = dlsym(hl, "e264hip_frame_preview");
+	if (g.stream && g.device_samples && g.slot_of && g.frame_device_ptr && g.frame_digest && g.preview_bytes && g.frame_preview) g.err = 0;
+}
+
+int e264front_bind_once(void)
+{
+	pthread_once(&g_once, bind_all);
+	return g.err;
 }
 
 /* A program that has loaded the front library and the back end itself (dlopen: a build of the front library that lies elsewhere, a variant of the back
- * end) hands over its two handles BEFORE the first e264front_frame_digest, so that the decoders it passes meet the instance that made them.  Without
- * this call the libraries are found as bind_all says.  0, or EINVAL (a null handle) / EALREADY (the first digest has been asked for). */
+ * end) hands over its two handles BEFORE the first e264front_frame_digest or e264front_frame_preview (front_preview.c), so that the decoders it
+ * passes meet the instance that made them.  Without this call the libraries are found as bind_all says.  0, or EINVAL (a null handle) / EALREADY (the first digest or preview has been asked for). */
 PUBLIC int e264front_digest_use(void *front_lib, void *hip_lib)
 {
 	if (!front_lib || !hip_lib) return EINVAL;
@@ -91,19 +78,11 @@ PUBLIC int e264front_digest_use(void *front_lib, void *hip_lib)
 	return 0;
 }
 
-/* out[0..2] = the Y, Cb, Cr digests of the base view (view 0, fr->samples) or of the second MVC view (view 1, fr->samples_mvc) of a frame
- * edge264_get_frame has just handed out.  Blocks until the kernels that write the picture and the digest kernel behind them have run.
- * 0; EINVAL (a null argument, no such view, a plane that belongs to no frame of this decoder, a decoder without device); ENODEV (the front
- * library or the back end is not to be found, or lacks an entry point); or the back end's error (e264hip_last_error). */
-PUBLIC int e264front_frame_digest(Edge264Decoder *dec, const Edge264Frame *fr, int view, uint64_t out[3])
+int e264front_view_of(Edge264Decoder *dec, const Edge264Frame *fr, int view, E264Stream **stream, int *slot_out, E264View *v)
 {
-	if (!dec || !fr || !out || (view != 0 && view != 1)) return EINVAL;
-	pthread_once(&g_once, bind_all);
-	if (g.err) return g.err;
 	E264Stream *s = (E264Stream *)g.stream(dec);
 	if (!s) return EINVAL;
 	const uint8_t *const *pl = view ? fr->samples_mvc : fr->samples;
-	E264View v;
 	int slot = -1;
 	for (int i = 0; i < 3; i++) { /* the three planes of a view lie in one slot */
 		const int sl = pl[i] ? g.slot_of(dec, pl[i]) : -1;
@@ -117,8 +96,25 @@ PUBLIC int e264front_frame_digest(Edge264Decoder *dec, const Edge264Frame *fr, i
 	for (int i = 0; i < 3; i++) {
 		const int64_t off = (int64_t)(d0 - base) + (int64_t)(pl[i] - pl[0]);
 		if (off < 0 || off > (int64_t)UINT32_MAX) return EINVAL;
-		v.plane[i] = (E264PlaneView){(uint32_t)off, (uint32_t)(uint16_t)(i ? fr->stride_C : fr->stride_Y), (uint16_t)(i ? fr->width_C : fr->width_Y),
+		v->plane[i] = (E264PlaneView){(uint32_t)off, (uint32_t)(uint16_t)(i ? fr->stride_C : fr->stride_Y), (uint16_t)(i ? fr->width_C : fr->width_Y),
 			(uint16_t)(i ? fr->height_C : fr->height_Y)};
 	}
+	*stream = s; *slot_out = slot;
+	return 0;
+}
+
+/* out[0..2] = the Y, Cb, Cr digests of the base view (view 0, fr->samples) or of the second MVC view (view 1, fr->samples_mvc) of a frame
+ * edge264_get_frame has just handed out.  Blocks until the kernels that write the picture and the digest kernel behind them have run.
+ * 0; EINVAL (a null argument, no such view, a plane that belongs to no frame of this decoder, a decoder without device); ENODEV (the front
+ * library or the back end is not to be found, or lacks an entry point); or the back end's error (e264hip_last_error). */
+PUBLIC int e264front_frame_digest(Edge264Decoder *dec, const Edge264Frame *fr, int view, uint64_t out[3])
+{
+	if (!dec || !fr || !out || (view != 0 && view != 1)) return EINVAL;
+	int r = e264front_bind_once();
+	if (r) return r;
+	E264Stream *s;
+	E264View v;
+	int slot;
+	if ((r = e264front_view_of(dec, fr, view, &s, &slot, &v))) return r;
 	return g.frame_digest(s, slot, &v, out);
 }

@@ -120,6 +120,39 @@ int  e264hip_view_check(const E264View *v, size_t slot_bytes);
 int  e264hip_frame_digest(E264Stream *s, int slot, const E264View *view, uint64_t out[3]);
 int  e264hip_digest_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, uint64_t *out);
 
+/* ---- reduced previews of decoded pictures, computed on the device ---------------------------------------- */
+/* A small picture of every stream (a monitoring wall, a scene-change or black-frame detector, a low-resolution inference stage) without
+ * reading the full-size one back: the device reduces the picture where it lies by 2, 4 or 8 in each direction and hands out 1/4, 1/16 or
+ * 1/64 of the bytes.  The reference has no counterpart (include/edge264_preview.h's e264_preview_plane does the same arithmetic on an
+ * Edge264Frame's planes on the host).
+ *
+ * THE PREVIEW, version E264_PREVIEW_VERSION.  For one plane of w x h samples s[y][x] and a reduction k = log2_factor in {1, 2, 3}, f = 1 << k:
+ *     ow = (w + f - 1) >> k          oh = (h + f - 1) >> k
+ *     P[Y][X] = (sum over dy < f, dx < f of s[min(f Y + dy, h - 1)][min(f X + dx, w - 1)]  +  (1 << (2 k - 1))) >> 2 k
+ * A box that leaves the view repeats the view's last column or row; the divisor is always f * f, so the result is exact in integers.  The
+ * three planes of a view (E264View, above) are reduced independently, each over its own cropped view; the result stays 4:2:0, since
+ * ceil(ceil(w / 2) / f) = ceil(ceil(w / f) / 2).  One picture's preview is Y | Cb | Cr, each plane tight (ow bytes per row): the sum of
+ * ow_p * oh_p bytes.
+ *
+ * e264hip_preview_bytes (host only): that size, and in dims (may be NULL) ow, oh of Y, Cb, Cr; 0 for a null view, k outside 1..3 or a plane
+ *   without samples.
+ * e264hip_preview_batch: the preview of views[i] of slot slots[i] of streams[i] at out + i * pitch; only its e264hip_preview_bytes bytes there
+ *   are written, the rest of a pitch is left as it was.  e264hip_frame_preview is the batch of one with pitch = cap.  Both BLOCK until `out`
+ *   (ordinary host memory) is filled.
+ * Ordering and lifetime are the digest's: one kernel, queued on the streams' compute lane behind everything queued there; all streams of a
+ *   call belong to `dev` and share one lane; a stream may appear more than once; the call marks the lane as a fill does and waits for its own
+ *   event, never for the device.
+ * Errors: EINVAL (and nothing is queued) for a null pointer, n < 0, n > E264_PREVIEW_MAX_BATCH, k outside 1..3, a slot out of range or not
+ *   allocated, streams of two lanes, a view e264hip_view_check refuses for that slot's size, pitch or cap smaller than a picture's preview,
+ *   more than E264_PREVIEW_MAX_BYTES in one call; e264hip_last_error() names the cause.  n == 0 returns 0. */
+#define E264_PREVIEW_VERSION 1
+#define E264_PREVIEW_MAX_BATCH 4096
+#define E264_PREVIEW_MAX_BYTES (1u << 28)   /* of one call: the sum of the pictures' previews, each rounded up to 16 */
+size_t e264hip_preview_bytes(const E264View *v, int log2_factor, uint16_t dims[6]);
+int  e264hip_frame_preview(E264Stream *s, int slot, const E264View *view, int log2_factor, void *out, size_t cap);
+int  e264hip_preview_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n,
+                           int log2_factor, void *out, size_t pitch);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
