@@ -37,6 +37,10 @@ class View(C.Structure):  # E264View: Y, Cb, Cr
 DIGEST_MAX_BATCH = 4096
 PREVIEW_MAX_BATCH = 4096
 PREVIEW_MAX_BYTES = 1 << 28
+DIFF_MAX_BATCH = 4096
+DIFF_NONE = 0xffffffff
+# E264Diff as numpy sees it: an array of shape (n, 3) -- pictures, then Y, Cb, Cr -- of this record (E264PlaneDiff, 32 bytes)
+DIFF_DTYPE = np.dtype([("sad", "<u8"), ("sse", "<u8"), ("count", "<u4"), ("first", "<u4"), ("max", "<u4"), ("zero", "<u4")])
 
 
 def as_view(view) -> View:
@@ -109,6 +113,9 @@ def load_library():
         "e264hip_preview_bytes": (sz, [C.POINTER(View), i, C.POINTER(C.c_uint16)]),
         "e264hip_frame_preview": (i, [vp, i, C.POINTER(View), i, vp, sz]),
         "e264hip_preview_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, i, vp, sz]),
+        "e264hip_diff_check": (i, [C.POINTER(View), sz, C.POINTER(View), sz]),
+        "e264hip_frame_diff": (i, [vp, i, C.POINTER(View), vp, i, C.POINTER(View), vp]),
+        "e264hip_diff_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -135,6 +142,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_kernel_timing", "e264hip_kernel_time_ms", "e264hip_set_option", "e264hip_build_flags", "e264hip_frame_device_ptr",
     "e264hip_launch_counts", "e264hip_view_check", "e264hip_frame_digest", "e264hip_digest_batch",
     "e264hip_preview_bytes", "e264hip_frame_preview", "e264hip_preview_batch",
+    "e264hip_diff_check", "e264hip_frame_diff", "e264hip_diff_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -161,6 +169,11 @@ def preview_dims(view, k: int):
 def preview_bytes(view, k: int) -> int:
     """e264hip_preview_bytes: the bytes of a view's preview at reduction k (Y | Cb | Cr, each plane tight); 0 for what has none.  Host only."""
     return int(load_library().e264hip_preview_bytes(C.byref(as_view(view)) if view is not None else None, k, None))
+
+
+def diff_check(view_a, slot_bytes_a: int, view_b, slot_bytes_b: int) -> int:
+    """e264hip_diff_check: 0, or EINVAL (last_error() names the cause) for a pair of views a difference record cannot be made of.  Host only."""
+    return int(load_library().e264hip_diff_check(C.byref(as_view(view_a)), slot_bytes_a, C.byref(as_view(view_b)), slot_bytes_b))
 
 
 def _split_preview(buf: np.ndarray, dims):
@@ -331,6 +344,20 @@ class Device:
         _check(self.L, self.L.e264hip_digest_batch(self.h, sa, la, va, n, out.ctypes.data_as(C.POINTER(C.c_uint64))), "digest_batch")
         return out
 
+    def diff_batch(self, streams_a, slots_a, views_a, streams_b, slots_b, views_b) -> np.ndarray:
+        """The difference records (include/edge264_hip.h, version 1) of views_a[k] of slot slots_a[k] of streams_a[k] against views_b[k] of slot slots_b[k] of
+        streams_b[k], computed on the device behind everything queued on the streams' lane, in one kernel.  Returns a structured array of shape (n, 3) and
+        dtype DIFF_DTYPE: [k][p]["sad" | "sse" | "count" | "first" | "max"] for plane p = Y, Cb, Cr ("first" is DIFF_NONE for equal planes).  Blocks."""
+        n = len(streams_a)
+        if not (len(slots_a) == len(views_a) == len(streams_b) == len(slots_b) == len(views_b) == n):
+            raise ValueError("diff_batch: the six lists differ in length")
+        out = np.zeros((n, 3), DIFF_DTYPE)
+        sa, sb = (C.c_void_p * n)(*[s.h for s in streams_a]), (C.c_void_p * n)(*[s.h for s in streams_b])
+        la, lb = (C.c_int * n)(*slots_a), (C.c_int * n)(*slots_b)
+        va, vb = (View * n)(*[as_view(v) for v in views_a]), (View * n)(*[as_view(v) for v in views_b])
+        _check(self.L, self.L.e264hip_diff_batch(self.h, sa, la, va, sb, lb, vb, n, out.ctypes.data), "diff_batch")
+        return out
+
     def preview_batch(self, streams, slots, views, k: int = 3):
         """The previews (include/edge264_hip.h, version 1: box filter by 1 << k, k = 1, 2, 3) of views[i] of slot slots[i] of streams[i], computed on the
         device behind everything queued on the streams' lane: a list of [Y, Cb, Cr] 2-D uint8 arrays, in call order.  Blocks."""
@@ -437,6 +464,21 @@ class Stream:
         out = (C.c_uint64 * 3)()
         _check(self.L, self.L.e264hip_frame_digest(self.h, slot, C.byref(as_view(view)), out), "frame_digest")
         return tuple(int(x) for x in out)
+
+    def diff(self, slot: int, view=None, other=None, other_slot=None, other_view=None) -> np.ndarray:
+        """The difference record of the picture in `slot` against the picture in `other_slot` of stream `other` (default: this stream, the same slot),
+        computed on the device behind everything queued for the streams: a structured array of shape (3,) and dtype DIFF_DTYPE (Y, Cb, Cr).  view,
+        other_view: as for digest; default the whole picture of each stream in the reference's layout.  Blocks."""
+        from .digest import frame_view
+        other = self if other is None else other
+        other_slot = slot if other_slot is None else other_slot
+        if view is None:
+            view = frame_view(self.w, self.h_mbs)
+        if other_view is None:
+            other_view = frame_view(other.w, other.h_mbs)
+        out = np.zeros(3, DIFF_DTYPE)
+        _check(self.L, self.L.e264hip_frame_diff(self.h, slot, C.byref(as_view(view)), other.h, other_slot, C.byref(as_view(other_view)), out.ctypes.data), "frame_diff")
+        return out
 
     def preview(self, slot: int, view=None, k: int = 3):
         """[Y, Cb, Cr] of the picture in `slot` reduced by 1 << k (k = 1, 2, 3) in each direction, computed on the device behind everything queued for the

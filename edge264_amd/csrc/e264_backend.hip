@@ -886,6 +886,71 @@ API int e264hip_frame_preview(E264Stream *s, int slot, const E264View *view, int
 	return e264hip_preview_batch(s->dev, &s, &slot, view, 1, log2_factor, out, cap);
 }
 
+// Difference records of n pairs of pictures (include/edge264_hip.h), built like e264hip_digest_batch: one kernel on the streams' lane behind everything queued
+// there; ONE page-locked block [jobs | records] and one device block of the same shape, both from the recycler and back in it behind the call's own serial (sized
+// for n rounded up to 64).  On the lane, under dev->lock: the table's copy, ONE clear of the records (the workgroups add and max into them; `first` travels as
+// ~first, so that zeros are its start too), the kernel, the records' copy, the serial.  The wait is for that serial's event, outside the lock; then the records go
+// to `out` with every `first` turned round.
+API int e264hip_diff_batch(E264Device *dev, E264Stream *const *streams_a, const int *slots_a, const E264View *views_a,
+	E264Stream *const *streams_b, const int *slots_b, const E264View *views_b, int n, E264Diff *out)
+{
+	if (!dev || n < 0 || n > E264_DIFF_MAX_BATCH) return fail(EINVAL, "diff_batch: null device or n outside 0..4096");
+	if (n == 0) return 0;
+	if (!streams_a || !slots_a || !views_a || !streams_b || !slots_b || !views_b || !out) return fail(EINVAL, "diff_batch: null argument");
+	int r;
+	for (int i = 0; i < n; i++) {
+		if ((r = check_lane(dev, streams_a, i)) || (r = check_lane(dev, streams_b, i))) return r;
+		if (streams_b[i]->lane != streams_a[0]->lane) return fail(EINVAL, "the streams of a batch must be bound to one compute lane");
+		if (slots_a[i] < 0 || slots_a[i] >= E264_MAX_SLOTS || !streams_a[i]->h_table[slots_a[i]] || slots_b[i] < 0 || slots_b[i] >= E264_MAX_SLOTS || !streams_b[i]->h_table[slots_b[i]])
+			return fail(EINVAL, "diff_batch: slot out of range or not allocated");
+		if ((r = e264hip_diff_check(&views_a[i], streams_a[i]->slot_bytes[slots_a[i]], &views_b[i], streams_b[i]->slot_bytes[slots_b[i]]))) return r;
+	}
+	if (set_device(dev)) return EIO;
+	const int lane = streams_a[0]->lane;
+	const size_t cap = ((size_t)n + 63) & ~(size_t)63, jobs_bytes = cap * sizeof(E264DiffJob), bytes = jobs_bytes + cap * sizeof(E264Diff);
+	uint8_t *h = (uint8_t *)mem_acquire(dev, bytes, true), *d = h ? (uint8_t *)mem_acquire(dev, bytes, false) : nullptr;
+	if (!d) { mem_release(dev, h, bytes, true, 0, 0); return fail(ENOMEM, "diff_batch: job table"); }
+	E264DiffJob *jobs = (E264DiffJob *)h;
+	uint32_t max_chunks = 1;
+	for (int i = 0; i < n; i++) {
+		jobs[i].base_a = streams_a[i]->h_table[slots_a[i]];
+		jobs[i].slot_bytes_a = streams_a[i]->slot_bytes[slots_a[i]];
+		jobs[i].base_b = streams_b[i]->h_table[slots_b[i]];
+		jobs[i].slot_bytes_b = streams_b[i]->slot_bytes[slots_b[i]];
+		jobs[i].view_a = views_a[i];
+		jobs[i].view_b = views_b[i];
+		jobs[i].chunks = e264_diff_chunks(&views_a[i]);
+		max_chunks = std::max(max_chunks, jobs[i].chunks);
+	}
+	uint64_t serial;
+	hipError_t e;
+	{
+		std::lock_guard<std::mutex> g(dev->lock);
+		hipStream_t q = dev->q[lane];
+		e = hipMemcpyAsync(d, h, (size_t)n * sizeof(E264DiffJob), hipMemcpyHostToDevice, q);
+		if (e == hipSuccess) e = hipMemsetAsync(d + jobs_bytes, 0, (size_t)n * sizeof(E264Diff), q);
+		if (e == hipSuccess) e = e264_launch_diff((const E264DiffJob *)d, n, max_chunks, (E264Diff *)(d + jobs_bytes), q);
+		if (e == hipSuccess) e = hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, (size_t)n * sizeof(E264Diff), hipMemcpyDeviceToHost, q);
+		serial = next_serial(dev, lane); // (also after an error: whatever was queued reads the two blocks until the lane has passed this point)
+	}
+	r = e == hipSuccess ? serial_wait(dev, serial, lane) : fail(EIO, "diff_batch", e);
+	if (!r) {
+		memcpy(out, h + jobs_bytes, (size_t)n * sizeof(E264Diff));
+		for (int i = 0; i < n; i++)
+			for (int p = 0; p < 3; p++)
+				out[i].plane[p].first = ~out[i].plane[p].first; // (the kernel keeps ~first under a max)
+	}
+	mem_release(dev, h, bytes, true, serial, lane);
+	mem_release(dev, d, bytes, false, serial, lane);
+	return r;
+}
+
+API int e264hip_frame_diff(E264Stream *a, int slot_a, const E264View *view_a, E264Stream *b, int slot_b, const E264View *view_b, E264Diff *out)
+{
+	if (!a || !b) return fail(EINVAL, "frame_diff: null stream");
+	return e264hip_diff_batch(a->dev, &a, &slot_a, view_a, &b, &slot_b, view_b, 1, out);
+}
+
 API int e264hip_packet_upload(E264Device *dev, const void *packet, size_t bytes, E264Packet **out)
 {
 	if (!dev || !out) return fail(EINVAL, "null argument");

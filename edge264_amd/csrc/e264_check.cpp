@@ -237,6 +237,20 @@ API size_t e264hip_preview_bytes(const E264View *v, int log2_factor, uint16_t di
 	return bytes;
 }
 
+// What a difference record (include/edge264_hip.h) asks of one pair: each view sound for its own slot, and plane p of the two of one size -- the diff kernel
+// walks both pictures with A's widths and heights.
+API int e264hip_diff_check(const E264View *a, size_t slot_bytes_a, const E264View *b, size_t slot_bytes_b)
+{
+	static const char *const names[3] = {"Y", "Cb", "Cr"};
+	int r;
+	if (!a || !b) return fail(EINVAL, "diff_check: null view");
+	if ((r = e264hip_view_check(a, slot_bytes_a)) || (r = e264hip_view_check(b, slot_bytes_b))) return r;
+	for (int p = 0; p < 3; p++)
+		if (a->plane[p].width != b->plane[p].width || a->plane[p].height != b->plane[p].height)
+			return fail(EINVAL, "diff_check: the two views' planes differ in size", names[p]);
+	return 0;
+}
+
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.
 // e264hip_packet_fold takes every level; _compact2 keeps what it took when it was written (1 and 2), _compact is level 1.
 API size_t e264hip_packet_fold_bound(const void *packet, size_t bytes, int level)

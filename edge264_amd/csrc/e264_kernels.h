@@ -63,4 +63,20 @@ struct E264PreviewJob {
 extern "C" uint32_t e264_preview_chunks(const E264View *view, int k);
 extern "C" hipError_t e264_launch_preview(const E264PreviewJob *jobs, int n_jobs, uint32_t max_chunks, hipStream_t stream);
 
+// e264_diff_kernel (e264_diff.h, e264_diff.hip: a translation unit of its own).  One job = one pair of pictures to compare: slot, size and view of each side as for
+// a digest job -- no byte outside [base_a, base_a + slot_bytes_a) or [base_b, base_b + slot_bytes_b) is read -- where plane p of the two views has one width and
+// height (e264hip_diff_check).  chunks = e264_diff_chunks(view_a).
+struct E264DiffJob {
+	const uint8_t *base_a;
+	uint64_t slot_bytes_a;
+	const uint8_t *base_b;
+	uint64_t slot_bytes_b;
+	E264View view_a, view_b;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_diff_chunks(const E264View *view);
+// out[i] accumulates the record of job i with `first` kept as ~first under a max: the caller clears out (n_jobs records) on `stream` in front and turns every
+// `first` round (first = ~first) after the copy down.  max_chunks: the largest chunks among the jobs.
+extern "C" hipError_t e264_launch_diff(const E264DiffJob *jobs, int n_jobs, uint32_t max_chunks, E264Diff *out, hipStream_t stream);
+
 #endif

@@ -11,7 +11,7 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
@@ -22,7 +22,12 @@
 // pictures nothing else verifies.  A VERIFICATION mode: every frame's digest is a blocking call, and frames are fetched only when the decoder's
 // queued packets have left for the device (as with read-back), so its frame rate is not the product's.  --preview writes s<k>.preview: every output frame's, and
 // every view's, reduced preview (include/edge264_hip.h, version 1: Y | Cb | Cr reduced by 1 << K in each direction, K = --preview-log2, default 3), the bytes one
-// after the other, computed on the device as well; bound and ordered like --digest, and both may be given.  Prints one JSON line with the throughput.
+// after the other, computed on the device as well; bound and ordered like --digest, and both may be given.  --diff writes s<k>.diff: for every output frame
+// and view from the stream's second frame on, one line with the difference record (include/edge264_hip.h, version 1) against the same view of the stream's PREVIOUS
+// output frame -- `count sad sse max first` for Y, Cb, Cr, 15 decimal numbers, first as `-` where there is none; the line `size` where the two frames' dimensions
+// differ -- computed on the device from the two pictures where they lie.  A MONITORING mode (freeze and scene-change detection): frames are fetched with borrow = 1,
+// one per stream is kept until the next frame has been compared with it (and goes back with edge264_return_frame then, or at the stream's end); bound and ordered
+// like --digest, and may be combined with it and with --preview.  Without --diff the driver's calls are what they were.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -55,6 +60,9 @@ struct Edge264Frame {
 	void *return_arg;
 };
 
+// E264Diff of include/edge264_hip.h (layout restated, as Edge264Frame above)
+struct E264DiffRecord { struct { uint64_t sad, sse; uint32_t count, first, max, zero; } plane[3]; };
+
 struct Front {
 	void *(*alloc)(int, void *, void *, int, void *, void *, void *);
 	int (*decode_NAL)(void *, const uint8_t *, const uint8_t *, void *, void *);
@@ -73,6 +81,8 @@ struct Front {
 	void *(*device_of)(void *);
 	int (*frame_digest)(void *, const Edge264Frame *, int, uint64_t *); // (bound with --digest only)
 	int (*frame_preview)(void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --preview only)
+	int (*frame_diff)(void *, const Edge264Frame *, int, void *, const Edge264Frame *, int, E264DiffRecord *); // (bound with --diff only, as return_frame)
+	void (*return_frame)(void *, void *);
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -100,6 +110,9 @@ struct Stream {
 	FILE *out = nullptr;
 	FILE *dig = nullptr;   // --digest: s<k>.digest
 	FILE *prev = nullptr;  // --preview: s<k>.preview
+	FILE *dif = nullptr;   // --diff: s<k>.diff
+	Edge264Frame kept;     // --diff: the previous output frame, borrowed (has_kept), until the next one has been compared with it
+	bool has_kept = false;
 	struct Pkt { void *data; size_t bytes; };
 	std::deque<Pkt> q;     // parsed, not yet submitted (guarded by the queue mutex)
 	std::atomic<bool> finished{false}; // its worker will queue nothing more (read outside `mu` by the other workers)
@@ -134,7 +147,7 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir;
 	std::vector<int> devices; // --devices
 	int preview_log2 = 3; // --preview-log2 K: previews are reduced by 1 << K (1, 2 or 3)
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
@@ -167,21 +180,26 @@ int main(int argc, char **argv)
 		else if (a == "--digest") digest_dir = next();
 		else if (a == "--preview") preview_dir = next();
 		else if (a == "--preview-log2") preview_log2 = atoi(next().c_str());
+		else if (a == "--diff") diff_dir = next();
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--dump-packets FILE] a.264 ...\n"
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--dump-packets FILE] a.264 ...\n"
 			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
 			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n"
 			"  --preview DIR writes DIR/s<k>.preview: every output frame's and view's preview (Y | Cb | Cr reduced by 1 << K, --preview-log2 K = 1, 2 or 3, default 3),\n"
-			"                computed on the device; bound and ordered like --digest\n");
+			"                computed on the device; bound and ordered like --digest\n"
+			"  --diff DIR    a monitoring mode: writes DIR/s<k>.diff, one line per output frame and view from the second frame on: count sad sse max first of Y, Cb, Cr\n"
+			"                against the stream's previous output frame (first: - where the planes are equal; the line `size` where the dimensions differ),\n"
+			"                computed on the device; frames are borrowed, one per stream is kept; bound and ordered like --digest\n");
 		return 2;
 	}
 	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
 	if (!preview_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --preview needs the device (not --parse-only)\n"); return 2; }
+	if (!diff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --diff needs the device (not --parse-only)\n"); return 2; }
 	if (preview_log2 < 1 || preview_log2 > 3) { fprintf(stderr, "e264_multi: --preview-log2 is 1, 2 or 3\n"); return 2; }
-	const bool on_device = !digest_dir.empty() || !preview_dir.empty(); // a pass that reads the pictures where they lie
+	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty(); // a pass that reads the pictures where they lie
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -194,7 +212,7 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
-	F.frame_digest = nullptr; F.frame_preview = nullptr;
+	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr;
 	if (on_device) { // e264front_frame_digest and e264front_frame_preview live in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
 		const size_t slash = front_path.rfind('/');
 		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
@@ -210,6 +228,7 @@ int main(int argc, char **argv)
 		if (!dl) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; }
 		if (!digest_dir.empty()) bind(dl, "e264front_frame_digest", F.frame_digest);
 		if (!preview_dir.empty()) bind(dl, "e264front_frame_preview", F.frame_preview);
+		if (!diff_dir.empty()) { bind(dl, "e264front_frame_diff", F.frame_diff); bind(fl, "edge264_return_frame", F.return_frame); }
 		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
 		int (*use)(void *, void *) = nullptr;
 		bind(dl, "e264front_digest_use", use);
@@ -260,6 +279,11 @@ int main(int argc, char **argv)
 				t.prev = fopen(o.c_str(), "wb");
 				if (!t.prev) { perror(o.c_str()); return 2; }
 			}
+			if (!diff_dir.empty()) {
+				std::string o = diff_dir + "/s" + std::to_string(S.size() - 1) + ".diff";
+				t.dif = fopen(o.c_str(), "w");
+				if (!t.dif) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -269,10 +293,15 @@ int main(int argc, char **argv)
 		}
 	FILE *dump = dump_path.empty() ? nullptr : fopen(dump_path.c_str(), "wb");
 
+	// --diff: the kept frame goes back to its decoder (after the next frame's comparison, before a flush, at the stream's end)
+	auto return_kept = [&](Stream &s) {
+		if (s.has_kept) F.return_frame(s.dec, s.kept.return_arg);
+		s.has_kept = false;
+	};
 	auto drain = [&](Stream &s) {
 		Edge264Frame fr;
 		long n = 0;
-		while (F.get_frame(s.dec, &fr, 0) == 0) {
+		while (F.get_frame(s.dec, &fr, s.dif ? 1 : 0) == 0) {
 			s.frames++; n++;
 			if (s.out) write_frame(s.out, fr);
 			if (s.dig)
@@ -293,6 +322,24 @@ int main(int argc, char **argv)
 					if (r) { fprintf(stderr, "e264front_frame_preview: %d (%s)\n", r, H.last_error()); _exit(1); }
 					fwrite(buf.data(), 1, (size_t)dims[0] * dims[1] + (size_t)dims[2] * dims[3] + (size_t)dims[4] * dims[5], s.prev);
 				}
+			if (s.dif) {
+				for (int v = 0; v < 2 && s.has_kept; v++) { // MVC: the second view's line follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					if (!(v ? s.kept.samples_mvc : s.kept.samples)[0] || fr.width_Y != s.kept.width_Y || fr.height_Y != s.kept.height_Y || fr.width_C != s.kept.width_C ||
+						fr.height_C != s.kept.height_C) { fprintf(s.dif, "size\n"); continue; }
+					E264DiffRecord d;
+					const int r = F.frame_diff(s.dec, &fr, v, s.dec, &s.kept, v, &d);
+					if (r) { fprintf(stderr, "e264front_frame_diff: %d (%s)\n", r, H.last_error()); _exit(1); }
+					for (int p = 0; p < 3; p++) {
+						fprintf(s.dif, "%s%u %llu %llu %u ", p ? " " : "", d.plane[p].count, (unsigned long long)d.plane[p].sad, (unsigned long long)d.plane[p].sse, d.plane[p].max);
+						if (d.plane[p].first == 0xffffffffu) fprintf(s.dif, "-");
+						else fprintf(s.dif, "%u", d.plane[p].first);
+					}
+					fprintf(s.dif, "\n");
+				}
+				return_kept(s);
+				s.kept = fr; s.has_kept = true;
+			}
 		}
 		return n;
 	};
@@ -335,6 +382,9 @@ int main(int argc, char **argv)
 				const long long t_dr = now_ns();
 				const long n_out = drain(s);
 				ns_drain += now_ns() - t_dr;
+				// --diff: at the end of a sequence and at a change of SPS the decoder wants EVERY frame back before it goes on (bump_all_frames,
+				// src/edge264_headers.c:97-104), the kept one too: the comparison starts again with the next sequence's first frame
+				if (n_out == 0 && s.has_kept) { return_kept(s); continue; }
 				if (n_out == 0) {
 					// ENOBUFS and nothing to hand out: a picture that will never complete (one of its slices failed and never came again) holds the
 					// frame buffers, and the same NAL would return ENOBUFS for ever (until round 5 this loop did exactly that).  edge264_flush is
@@ -346,6 +396,7 @@ int main(int argc, char **argv)
 						std::lock_guard<std::mutex> lk(mu);
 						if (!s.q.empty()) return BLOCKED;
 					}
+					return_kept(s); // (--diff: nothing of this decoder stays borrowed over a flush; the comparison starts again with the next frame)
 					F.flush(s.dec);
 					s.just_flushed = true;
 					stuck_flushes++;
@@ -525,10 +576,12 @@ int main(int argc, char **argv)
 	double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 	for (Stream &s : S) {
 		drain(s);
+		return_kept(s);
 		total_frames += s.frames;
 		if (s.out) fclose(s.out);
 		if (s.dig) fclose(s.dig);
 		if (s.prev) fclose(s.prev);
+		if (s.dif) fclose(s.dif);
 		F.free_dec(&s.dec);
 	}
 	if (dump) fclose(dump);

@@ -153,6 +153,46 @@ int  e264hip_frame_preview(E264Stream *s, int slot, const E264View *view, int lo
 int  e264hip_preview_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n,
                            int log2_factor, void *out, size_t pitch);
 
+/* ---- two decoded pictures compared on the device: the per-plane difference record ------------------------ */
+/* How two pictures in HBM relate (consecutive output pictures of a stream for a freeze or scene-change detector, two renditions of one
+ * content for PSNR, a picture whose digest did not match against the expected one) without reading either back.  The reference has no
+ * counterpart (include/edge264_diff.h's e264_diff_plane does the same arithmetic on two Edge264Frames' planes on the host).
+ *
+ * THE DIFFERENCE RECORD, version E264_DIFF_VERSION.  For plane p of view A and of view B, both w x h samples, i = y * w + x, d_i = |a_i - b_i|:
+ *     sad = sum of d_i      sse = sum of d_i^2      count = the number of i with d_i != 0      max = max d_i (0 for equal planes)
+ *     first = the smallest i with d_i != 0, E264_DIFF_NONE where there is none (the largest index of a view is 65535^2 - 1 < E264_DIFF_NONE)
+ *     zero = 0
+ * Each plane is indexed from 0 over its own (cropped) view, row-major, as for the digest.  Everything is exact in integers for every view
+ * e264hip_view_check accepts: count < 2^32, sad < 2^40, sse < 2^48.  Every member is a sum, a max or a min, so every split over lanes, waves
+ * and workgroups, and every order in which workgroups finish, gives the same record.
+ * PSNR is not part of the record: it is 10 log10(255^2 w h / sse), infinite for sse == 0 (edge264_amd/diff.py: psnr).
+ *
+ * e264hip_diff_batch: out[i] = views_a[i] of slot slots_a[i] of streams_a[i] against views_b[i] of slot slots_b[i] of streams_b[i];
+ *   e264hip_frame_diff is the batch of one.  Both BLOCK until `out` (ordinary host memory) is filled.  A and B may be different streams, the same
+ *   stream, even the same slot and view (the record is then all zero, with first = E264_DIFF_NONE).
+ * Ordering: one kernel per call, whatever n, queued on the streams' compute lane behind everything queued there -- a diff asked for right after
+ *   e264hip_frame_submit, e264hip_submit_batch*, e264hip_frame_fill or e264hip_frame_upload, with no wait between, sees that work's result.  All
+ *   streams of a call, on both sides, belong to `dev` and share one lane, as for a submission (else EINVAL); a stream may appear more than once (the
+ *   pass only reads).  The call waits for its own event, never for the device.
+ * Lifetime: the call marks the lane as a fill does, so a slot freed while it runs stays parked behind it (e264hip_frame_free never hands memory
+ *   back under a kernel); the caller drives the streams, as for a submission.
+ * Errors: EINVAL (and nothing is queued, `out` is untouched) for a null pointer, n < 0, n > E264_DIFF_MAX_BATCH, a slot out of range or not allocated,
+ *   streams of two devices or two lanes, a view e264hip_view_check refuses for its own slot's size (either side), plane p of A and of B differing in
+ *   width or height for any p; e264hip_last_error() names the cause.  n == 0 returns 0.
+ * e264hip_diff_check (host only, like e264hip_view_check): what the two calls ask of one pair of views and their slots' sizes; 0 or EINVAL with a text. */
+typedef struct { uint64_t sad, sse; uint32_t count, first, max, zero; } E264PlaneDiff; /* 32 bytes */
+typedef struct { E264PlaneDiff plane[3]; } E264Diff;                                    /* Y, Cb, Cr: 96 bytes */
+#define E264_DIFF_VERSION 1
+#define E264_DIFF_NONE 0xffffffffu
+#define E264_DIFF_MAX_BATCH 4096
+int  e264hip_diff_check(const E264View *view_a, size_t slot_bytes_a, const E264View *view_b, size_t slot_bytes_b);
+int  e264hip_frame_diff(E264Stream *a, int slot_a, const E264View *view_a,
+                        E264Stream *b, int slot_b, const E264View *view_b, E264Diff *out);
+int  e264hip_diff_batch(E264Device *dev,
+                        E264Stream *const *streams_a, const int *slots_a, const E264View *views_a,
+                        E264Stream *const *streams_b, const int *slots_b, const E264View *views_b,
+                        int n, E264Diff *out);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
