@@ -41,6 +41,7 @@ DIFF_MAX_BATCH = 4096
 DIFF_NONE = 0xffffffff
 # E264Diff as numpy sees it: an array of shape (n, 3) -- pictures, then Y, Cb, Cr -- of this record (E264PlaneDiff, 32 bytes)
 DIFF_DTYPE = np.dtype([("sad", "<u8"), ("sse", "<u8"), ("count", "<u4"), ("first", "<u4"), ("max", "<u4"), ("zero", "<u4")])
+HIST_MAX_BATCH = 4096  # E264Hist as numpy sees it: uint32 of shape (n, 3, 256) -- pictures, then Y, Cb, Cr, then the sample value
 
 
 def as_view(view) -> View:
@@ -116,6 +117,8 @@ def load_library():
         "e264hip_diff_check": (i, [C.POINTER(View), sz, C.POINTER(View), sz]),
         "e264hip_frame_diff": (i, [vp, i, C.POINTER(View), vp, i, C.POINTER(View), vp]),
         "e264hip_diff_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, vp]),
+        "e264hip_frame_hist": (i, [vp, i, C.POINTER(View), vp]),
+        "e264hip_hist_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -143,6 +146,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_launch_counts", "e264hip_view_check", "e264hip_frame_digest", "e264hip_digest_batch",
     "e264hip_preview_bytes", "e264hip_frame_preview", "e264hip_preview_batch",
     "e264hip_diff_check", "e264hip_frame_diff", "e264hip_diff_batch",
+    "e264hip_frame_hist", "e264hip_hist_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -358,6 +362,19 @@ class Device:
         _check(self.L, self.L.e264hip_diff_batch(self.h, sa, la, va, sb, lb, vb, n, out.ctypes.data), "diff_batch")
         return out
 
+    def hist_batch(self, streams, slots, views) -> np.ndarray:
+        """The histogram records (include/edge264_hip.h, version 1) of views[k] of slot slots[k] of streams[k], computed on the device behind everything
+        queued on the streams' lane, in one kernel: a uint32 array of shape (n, 3, 256), [k][p][v] = the samples of plane p = Y, Cb, Cr equal to v.  Blocks."""
+        n = len(streams)
+        if not (len(slots) == len(views) == n):
+            raise ValueError("hist_batch: the three lists differ in length")
+        out = np.zeros((n, 3, 256), np.uint32)
+        sa = (C.c_void_p * n)(*[s.h for s in streams])
+        la = (C.c_int * n)(*slots)
+        va = (View * n)(*[as_view(v) for v in views])
+        _check(self.L, self.L.e264hip_hist_batch(self.h, sa, la, va, n, out.ctypes.data), "hist_batch")
+        return out
+
     def preview_batch(self, streams, slots, views, k: int = 3):
         """The previews (include/edge264_hip.h, version 1: box filter by 1 << k, k = 1, 2, 3) of views[i] of slot slots[i] of streams[i], computed on the
         device behind everything queued on the streams' lane: a list of [Y, Cb, Cr] 2-D uint8 arrays, in call order.  Blocks."""
@@ -478,6 +495,16 @@ class Stream:
             other_view = frame_view(other.w, other.h_mbs)
         out = np.zeros(3, DIFF_DTYPE)
         _check(self.L, self.L.e264hip_frame_diff(self.h, slot, C.byref(as_view(view)), other.h, other_slot, C.byref(as_view(other_view)), out.ctypes.data), "frame_diff")
+        return out
+
+    def hist(self, slot: int, view=None) -> np.ndarray:
+        """The histogram record of the picture in `slot`, computed on the device behind everything queued for the stream: a uint32 array of shape
+        (3, 256), [p][v] = the samples of plane p = Y, Cb, Cr equal to v.  view: as for digest; default the whole picture in the reference's layout.  Blocks."""
+        from .digest import frame_view
+        if view is None:
+            view = frame_view(self.w, self.h_mbs)
+        out = np.zeros((3, 256), np.uint32)
+        _check(self.L, self.L.e264hip_frame_hist(self.h, slot, C.byref(as_view(view)), out.ctypes.data), "frame_hist")
         return out
 
     def preview(self, slot: int, view=None, k: int = 3):

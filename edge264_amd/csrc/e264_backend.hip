@@ -951,6 +951,59 @@ API int e264hip_frame_diff(E264Stream *a, int slot_a, const E264View *view_a, E2
 	return e264hip_diff_batch(a->dev, &a, &slot_a, view_a, &b, &slot_b, view_b, 1, out);
 }
 
+// Histogram records of n pictures (include/edge264_hip.h), built like e264hip_diff_batch: one kernel on the streams' lane behind everything queued there; ONE
+// page-locked block [jobs | records] and one device block of the same shape, both from the recycler and back in it behind the call's own serial (sized for n
+// rounded up to 64).  On the lane, under dev->lock: the table's copy, ONE clear of the records (the workgroups add into them), the kernel, the records' copy, the
+// serial.  The wait is for that serial's event, outside the lock; then the records go to `out`.
+API int e264hip_hist_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, E264Hist *out)
+{
+	if (!dev || n < 0 || n > E264_HIST_MAX_BATCH) return fail(EINVAL, "hist_batch: null device or n outside 0..4096");
+	if (n == 0) return 0;
+	if (!streams || !slots || !views || !out) return fail(EINVAL, "hist_batch: null argument");
+	int r;
+	for (int i = 0; i < n; i++) {
+		if ((r = check_lane(dev, streams, i))) return r;
+		if (slots[i] < 0 || slots[i] >= E264_MAX_SLOTS || !streams[i]->h_table[slots[i]]) return fail(EINVAL, "hist_batch: slot out of range or not allocated");
+		if ((r = e264hip_view_check(&views[i], streams[i]->slot_bytes[slots[i]]))) return r;
+	}
+	if (set_device(dev)) return EIO;
+	const int lane = streams[0]->lane;
+	const size_t cap = ((size_t)n + 63) & ~(size_t)63, jobs_bytes = cap * sizeof(E264HistJob), bytes = jobs_bytes + cap * sizeof(E264Hist);
+	uint8_t *h = (uint8_t *)mem_acquire(dev, bytes, true), *d = h ? (uint8_t *)mem_acquire(dev, bytes, false) : nullptr;
+	if (!d) { mem_release(dev, h, bytes, true, 0, 0); return fail(ENOMEM, "hist_batch: job table"); }
+	E264HistJob *jobs = (E264HistJob *)h;
+	uint32_t max_chunks = 1;
+	for (int i = 0; i < n; i++) {
+		jobs[i].base = streams[i]->h_table[slots[i]];
+		jobs[i].slot_bytes = streams[i]->slot_bytes[slots[i]];
+		jobs[i].view = views[i];
+		jobs[i].chunks = e264_hist_chunks(&views[i]);
+		max_chunks = std::max(max_chunks, jobs[i].chunks);
+	}
+	uint64_t serial;
+	hipError_t e;
+	{
+		std::lock_guard<std::mutex> g(dev->lock);
+		hipStream_t q = dev->q[lane];
+		e = hipMemcpyAsync(d, h, (size_t)n * sizeof(E264HistJob), hipMemcpyHostToDevice, q);
+		if (e == hipSuccess) e = hipMemsetAsync(d + jobs_bytes, 0, (size_t)n * sizeof(E264Hist), q);
+		if (e == hipSuccess) e = e264_launch_hist((const E264HistJob *)d, n, max_chunks, (E264Hist *)(d + jobs_bytes), q);
+		if (e == hipSuccess) e = hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, (size_t)n * sizeof(E264Hist), hipMemcpyDeviceToHost, q);
+		serial = next_serial(dev, lane); // (also after an error: whatever was queued reads the two blocks until the lane has passed this point)
+	}
+	r = e == hipSuccess ? serial_wait(dev, serial, lane) : fail(EIO, "hist_batch", e);
+	if (!r) memcpy(out, h + jobs_bytes, (size_t)n * sizeof(E264Hist));
+	mem_release(dev, h, bytes, true, serial, lane);
+	mem_release(dev, d, bytes, false, serial, lane);
+	return r;
+}
+
+API int e264hip_frame_hist(E264Stream *s, int slot, const E264View *view, E264Hist *out)
+{
+	if (!s) return fail(EINVAL, "frame_hist: null stream");
+	return e264hip_hist_batch(s->dev, &s, &slot, view, 1, out);
+}
+
 API int e264hip_packet_upload(E264Device *dev, const void *packet, size_t bytes, E264Packet **out)
 {
 	if (!dev || !out) return fail(EINVAL, "null argument");

@@ -79,4 +79,16 @@ extern "C" uint32_t e264_diff_chunks(const E264View *view);
 // `first` round (first = ~first) after the copy down.  max_chunks: the largest chunks among the jobs.
 extern "C" hipError_t e264_launch_diff(const E264DiffJob *jobs, int n_jobs, uint32_t max_chunks, E264Diff *out, hipStream_t stream);
 
+// e264_hist_kernel (e264_hist.h, e264_hist.hip: a translation unit of its own).  One job = one picture to count: slot, size and view as for a digest job -- no
+// byte outside [base, base + slot_bytes) is read.  chunks = e264_hist_chunks(view).
+struct E264HistJob {
+	const uint8_t *base;
+	uint64_t slot_bytes;
+	E264View view;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_hist_chunks(const E264View *view);
+// out[i] accumulates the record of job i: the caller clears out (n_jobs records) on `stream` in front.  max_chunks: the largest chunks among the jobs.
+extern "C" hipError_t e264_launch_hist(const E264HistJob *jobs, int n_jobs, uint32_t max_chunks, E264Hist *out, hipStream_t stream);
+
 #endif

@@ -11,7 +11,7 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
@@ -27,7 +27,10 @@
 // output frame -- `count sad sse max first` for Y, Cb, Cr, 15 decimal numbers, first as `-` where there is none; the line `size` where the two frames' dimensions
 // differ -- computed on the device from the two pictures where they lie.  A MONITORING mode (freeze and scene-change detection): frames are fetched with borrow = 1,
 // one per stream is kept until the next frame has been compared with it (and goes back with edge264_return_frame then, or at the stream's end); bound and ordered
-// like --digest, and may be combined with it and with --preview.  Without --diff the driver's calls are what they were.  Prints one JSON line with the throughput.
+// like --digest, and may be combined with it and with --preview.  Without --diff the driver's calls are what they were.  --hist writes s<k>.hist: for every output
+// frame and view the 3072 bytes of the histogram record (include/edge264_hip.h, version 1: 256 little-endian 32-bit counts for Y, then Cb, then Cr), one after the
+// other, computed on the device where the picture lies; bound and ordered like --digest, and may be combined with it, with --preview and with --diff.  Without
+// --hist the driver's calls are what they were.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -62,6 +65,8 @@ struct Edge264Frame {
 
 // E264Diff of include/edge264_hip.h (layout restated, as Edge264Frame above)
 struct E264DiffRecord { struct { uint64_t sad, sse; uint32_t count, first, max, zero; } plane[3]; };
+// E264Hist of include/edge264_hip.h (the same)
+struct E264HistRecord { uint32_t bin[3][256]; };
 
 struct Front {
 	void *(*alloc)(int, void *, void *, int, void *, void *, void *);
@@ -83,6 +88,7 @@ struct Front {
 	int (*frame_preview)(void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --preview only)
 	int (*frame_diff)(void *, const Edge264Frame *, int, void *, const Edge264Frame *, int, E264DiffRecord *); // (bound with --diff only, as return_frame)
 	void (*return_frame)(void *, void *);
+	int (*frame_hist)(void *, const Edge264Frame *, int, E264HistRecord *); // (bound with --hist only)
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -111,6 +117,7 @@ struct Stream {
 	FILE *dig = nullptr;   // --digest: s<k>.digest
 	FILE *prev = nullptr;  // --preview: s<k>.preview
 	FILE *dif = nullptr;   // --diff: s<k>.diff
+	FILE *his = nullptr;   // --hist: s<k>.hist
 	Edge264Frame kept;     // --diff: the previous output frame, borrowed (has_kept), until the next one has been compared with it
 	bool has_kept = false;
 	struct Pkt { void *data; size_t bytes; };
@@ -147,7 +154,7 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir, hist_dir;
 	std::vector<int> devices; // --devices
 	int preview_log2 = 3; // --preview-log2 K: previews are reduced by 1 << K (1, 2 or 3)
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
@@ -181,25 +188,29 @@ int main(int argc, char **argv)
 		else if (a == "--preview") preview_dir = next();
 		else if (a == "--preview-log2") preview_log2 = atoi(next().c_str());
 		else if (a == "--diff") diff_dir = next();
+		else if (a == "--hist") hist_dir = next();
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--dump-packets FILE] a.264 ...\n"
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--dump-packets FILE] a.264 ...\n"
 			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
 			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n"
 			"  --preview DIR writes DIR/s<k>.preview: every output frame's and view's preview (Y | Cb | Cr reduced by 1 << K, --preview-log2 K = 1, 2 or 3, default 3),\n"
 			"                computed on the device; bound and ordered like --digest\n"
 			"  --diff DIR    a monitoring mode: writes DIR/s<k>.diff, one line per output frame and view from the second frame on: count sad sse max first of Y, Cb, Cr\n"
 			"                against the stream's previous output frame (first: - where the planes are equal; the line `size` where the dimensions differ),\n"
-			"                computed on the device; frames are borrowed, one per stream is kept; bound and ordered like --digest\n");
+			"                computed on the device; frames are borrowed, one per stream is kept; bound and ordered like --digest\n"
+			"  --hist DIR    writes DIR/s<k>.hist: every output frame's and view's histogram record (256 little-endian 32-bit counts of Y, then Cb, then Cr: 3072 bytes),\n"
+			"                computed on the device; bound and ordered like --digest\n");
 		return 2;
 	}
 	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
 	if (!preview_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --preview needs the device (not --parse-only)\n"); return 2; }
 	if (!diff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --diff needs the device (not --parse-only)\n"); return 2; }
+	if (!hist_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --hist needs the device (not --parse-only)\n"); return 2; }
 	if (preview_log2 < 1 || preview_log2 > 3) { fprintf(stderr, "e264_multi: --preview-log2 is 1, 2 or 3\n"); return 2; }
-	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty(); // a pass that reads the pictures where they lie
+	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty() || !hist_dir.empty(); // a pass that reads the pictures where they lie
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -212,7 +223,7 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
-	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr;
+	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr; F.frame_hist = nullptr;
 	if (on_device) { // e264front_frame_digest and e264front_frame_preview live in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
 		const size_t slash = front_path.rfind('/');
 		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
@@ -229,6 +240,7 @@ int main(int argc, char **argv)
 		if (!digest_dir.empty()) bind(dl, "e264front_frame_digest", F.frame_digest);
 		if (!preview_dir.empty()) bind(dl, "e264front_frame_preview", F.frame_preview);
 		if (!diff_dir.empty()) { bind(dl, "e264front_frame_diff", F.frame_diff); bind(fl, "edge264_return_frame", F.return_frame); }
+		if (!hist_dir.empty()) bind(dl, "e264front_frame_hist", F.frame_hist);
 		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
 		int (*use)(void *, void *) = nullptr;
 		bind(dl, "e264front_digest_use", use);
@@ -284,6 +296,11 @@ int main(int argc, char **argv)
 				t.dif = fopen(o.c_str(), "w");
 				if (!t.dif) { perror(o.c_str()); return 2; }
 			}
+			if (!hist_dir.empty()) {
+				std::string o = hist_dir + "/s" + std::to_string(S.size() - 1) + ".hist";
+				t.his = fopen(o.c_str(), "wb");
+				if (!t.his) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -321,6 +338,19 @@ int main(int argc, char **argv)
 					const int r = F.frame_preview(s.dec, &fr, v, preview_log2, buf.data(), buf.size(), dims);
 					if (r) { fprintf(stderr, "e264front_frame_preview: %d (%s)\n", r, H.last_error()); _exit(1); }
 					fwrite(buf.data(), 1, (size_t)dims[0] * dims[1] + (size_t)dims[2] * dims[3] + (size_t)dims[4] * dims[5], s.prev);
+				}
+			if (s.his)
+				for (int v = 0; v < 2; v++) { // MVC: the second view's record follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					E264HistRecord hr;
+					const int r = F.frame_hist(s.dec, &fr, v, &hr);
+					if (r) { fprintf(stderr, "e264front_frame_hist: %d (%s)\n", r, H.last_error()); _exit(1); }
+					uint8_t le[sizeof(hr)]; // little-endian whatever the host
+					for (size_t k = 0; k < 768; k++) {
+						const uint32_t n = hr.bin[k >> 8][k & 255];
+						le[4 * k] = (uint8_t)n; le[4 * k + 1] = (uint8_t)(n >> 8); le[4 * k + 2] = (uint8_t)(n >> 16); le[4 * k + 3] = (uint8_t)(n >> 24);
+					}
+					fwrite(le, 1, sizeof(le), s.his);
 				}
 			if (s.dif) {
 				for (int v = 0; v < 2 && s.has_kept; v++) { // MVC: the second view's line follows the base view's
@@ -582,6 +612,7 @@ int main(int argc, char **argv)
 		if (s.dig) fclose(s.dig);
 		if (s.prev) fclose(s.prev);
 		if (s.dif) fclose(s.dif);
+		if (s.his) fclose(s.his);
 		F.free_dec(&s.dec);
 	}
 	if (dump) fclose(dump);

@@ -1,6 +1,6 @@
 /*
- * front_bind.h -- internal to libedge264_frontdigest.so (front_digest.c, front_preview.c, front_diff.c): the entry points of the front library and of the back end
- * the three files work through, bound once for all (front_digest.c; e264front_digest_use names the libraries), and the view a frame's planes make
+ * front_bind.h -- internal to libedge264_frontdigest.so (front_digest.c, front_preview.c, front_diff.c, front_hist.c): the entry points of the front library and of the back end
+ * the four files work through, bound once for all (front_digest.c; e264front_digest_use names the libraries), and the view a frame's planes make
  * in their slot.  Nothing here is exported.
  */
 #ifndef E264_FRONT_BIND_H
@@ -35,6 +35,7 @@ struct E264FrontBind {
 	size_t (*preview_bytes)(const E264View *, int, uint16_t *);
 	int (*frame_preview)(E264Stream *, int, const E264View *, int, void *, size_t);
 	int (*frame_diff)(E264Stream *, int, const E264View *, E264Stream *, int, const E264View *, E264Diff *);
+	int (*frame_hist)(E264Stream *, int, const E264View *, E264Hist *);
 };
 extern HIDDEN struct E264FrontBind e264front_bind;
 

@@ -193,6 +193,36 @@ int  e264hip_diff_batch(E264Device *dev,
                         E264Stream *const *streams_b, const int *slots_b, const E264View *views_b,
                         int n, E264Diff *out);
 
+/* ---- histograms of decoded pictures, computed on the device ---------------------------------------------- */
+/* The distribution of a picture's own sample values (black-frame, flash and fade detectors, exposure and clipping meters, histogram-distance
+ * scene-cut detectors, auto-levels, entropy estimates) without reading the picture back: 3072 bytes come down instead of the picture.  A preview's
+ * histogram is not the picture's -- a box filter removes the extremes a clipping or black-level meter looks for -- and the difference record says
+ * nothing about levels.  The reference has no counterpart (include/edge264_hist.h's e264_hist_plane counts an Edge264Frame's planes on the host).
+ *
+ * THE HISTOGRAM RECORD, version E264_HIST_VERSION.  For plane p of a view (E264View, above: cropped, as for the digest):
+ *     bin[p][v] = the number of samples of the plane equal to v, for v in 0..255
+ * The record is exact: a view has at most 65535^2 < 2^32 samples per plane, so a bin cannot wrap, and the bins of a plane sum to width * height.
+ * Every bin is a sum, so every split over lanes, waves and workgroups, and every order of arrival, gives the same record.  The bins are the WHOLE
+ * record: count, min, max, sum, sum of squares, mean, variance and quantiles are arithmetic on 256 numbers and belong on the host
+ * (include/edge264_hist.h: e264_hist_stats, e264_hist_quantile; edge264_amd/hist.py: stats, quantile, distance).
+ *
+ * e264hip_hist_batch: out[i] = the record of views[i] of slot slots[i] of streams[i]; e264hip_frame_hist is the batch of one.  Both BLOCK until `out`
+ *   (ordinary host memory) is filled.
+ * Ordering: one kernel per call, whatever n, queued on the streams' compute lane behind everything queued there -- a histogram asked for right after
+ *   e264hip_frame_submit, e264hip_submit_batch*, e264hip_frame_fill or e264hip_frame_upload, with no wait between, sees that work's result.  All
+ *   streams of a call belong to `dev` and share one lane, as for a submission (else EINVAL); a stream may appear more than once (the pass only
+ *   reads).  The call waits for its own event, never for the device.
+ * Lifetime: the call marks the lane as a fill does, so a slot freed while it runs stays parked behind it (e264hip_frame_free never hands memory
+ *   back under a kernel); the caller drives the streams, as for a submission.
+ * Errors: EINVAL (and nothing is queued, `out` is untouched) for a null pointer, n < 0, n > E264_HIST_MAX_BATCH, a slot out of range or not allocated,
+ *   streams of two devices or two lanes, a view e264hip_view_check refuses for that slot's size; e264hip_last_error() names the cause.  n == 0
+ *   returns 0.  e264hip_view_check is the whole validation of a view: there is no check export of the histogram's own. */
+typedef struct { uint32_t bin[3][256]; } E264Hist;   /* Y, Cb, Cr: 3072 bytes */
+#define E264_HIST_VERSION 1
+#define E264_HIST_MAX_BATCH 4096
+int  e264hip_frame_hist(E264Stream *s, int slot, const E264View *view, E264Hist *out);
+int  e264hip_hist_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, E264Hist *out);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
