@@ -41,6 +41,10 @@ DIFF_MAX_BATCH = 4096
 DIFF_NONE = 0xffffffff
 # E264Diff as numpy sees it: an array of shape (n, 3) -- pictures, then Y, Cb, Cr -- of this record (E264PlaneDiff, 32 bytes)
 DIFF_DTYPE = np.dtype([("sad", "<u8"), ("sse", "<u8"), ("count", "<u4"), ("first", "<u4"), ("max", "<u4"), ("zero", "<u4")])
+BLOCKDIFF_MAX_BATCH = 4096
+BLOCKDIFF_MAX_BYTES = 1 << 28
+# E264BlockDiff as numpy sees it: a plane's map is an array of shape (bh, bw) of this record (8 bytes)
+BLOCKDIFF_DTYPE = np.dtype([("sad", "<u4"), ("sse", "<u4")])
 HIST_MAX_BATCH = 4096  # E264Hist as numpy sees it: uint32 of shape (n, 3, 256) -- pictures, then Y, Cb, Cr, then the sample value
 
 
@@ -119,6 +123,10 @@ def load_library():
         "e264hip_diff_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, vp]),
         "e264hip_frame_hist": (i, [vp, i, C.POINTER(View), vp]),
         "e264hip_hist_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, vp]),
+        "e264hip_blockdiff_bytes": (sz, [C.POINTER(View), i, C.POINTER(C.c_uint16)]),
+        "e264hip_blockdiff_check": (i, [C.POINTER(View), sz, C.POINTER(View), sz, i]),
+        "e264hip_frame_blockdiff": (i, [vp, i, C.POINTER(View), vp, i, C.POINTER(View), i, vp, sz]),
+        "e264hip_blockdiff_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, i, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -147,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_preview_bytes", "e264hip_frame_preview", "e264hip_preview_batch",
     "e264hip_diff_check", "e264hip_frame_diff", "e264hip_diff_batch",
     "e264hip_frame_hist", "e264hip_hist_batch",
+    "e264hip_blockdiff_bytes", "e264hip_blockdiff_check", "e264hip_frame_blockdiff", "e264hip_blockdiff_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -178,6 +187,33 @@ def preview_bytes(view, k: int) -> int:
 def diff_check(view_a, slot_bytes_a: int, view_b, slot_bytes_b: int) -> int:
     """e264hip_diff_check: 0, or EINVAL (last_error() names the cause) for a pair of views a difference record cannot be made of.  Host only."""
     return int(load_library().e264hip_diff_check(C.byref(as_view(view_a)), slot_bytes_a, C.byref(as_view(view_b)), slot_bytes_b))
+
+
+def blockdiff_dims(view, k: int):
+    """[(bw, bh)] of Y, Cb, Cr of a view's block difference map at block size 1 << k, from the library (host only); raises for what has none"""
+    d = (C.c_uint16 * 6)()
+    if not load_library().e264hip_blockdiff_bytes(C.byref(as_view(view)), k, d):
+        raise ValueError("blockdiff: k is 3, 4, 5 or 6 and every plane of the view has samples")
+    return [(int(d[2 * p]), int(d[2 * p + 1])) for p in range(3)]
+
+
+def blockdiff_bytes(view, k: int) -> int:
+    """e264hip_blockdiff_bytes: the bytes of a view's block difference map at block size 1 << k (Y | Cb | Cr, each plane tight); 0 for what has none.  Host only."""
+    return int(load_library().e264hip_blockdiff_bytes(C.byref(as_view(view)) if view is not None else None, k, None))
+
+
+def blockdiff_check(view_a, slot_bytes_a: int, view_b, slot_bytes_b: int, k: int) -> int:
+    """e264hip_blockdiff_check: 0, or EINVAL (last_error() names the cause) for a pair of views or a block size a map cannot be made of.  Host only."""
+    return int(load_library().e264hip_blockdiff_check(C.byref(as_view(view_a)), slot_bytes_a, C.byref(as_view(view_b)), slot_bytes_b, k))
+
+
+def _split_blockdiff(buf: np.ndarray, dims):
+    out, at = [], 0
+    for bw, bh in dims:
+        n = bw * bh * BLOCKDIFF_DTYPE.itemsize
+        out.append(buf[at:at + n].view(BLOCKDIFF_DTYPE).reshape(bh, bw))
+        at += n
+    return out
 
 
 def _split_preview(buf: np.ndarray, dims):
@@ -391,6 +427,24 @@ class Device:
         _check(self.L, self.L.e264hip_preview_batch(self.h, sa, la, va, n, k, out.ctypes.data, pitch), "preview_batch")
         return [_split_preview(out[j], dims[j]) for j in range(n)]
 
+    def blockdiff_batch(self, streams_a, slots_a, views_a, streams_b, slots_b, views_b, k: int = 4):
+        """The block difference maps (include/edge264_hip.h, version 1: blocks of 1 << k, k = 3 .. 6) of views_a[i] of slot slots_a[i] of streams_a[i] against
+        views_b[i] of slot slots_b[i] of streams_b[i], computed on the device behind everything queued on the streams' lane, in one kernel: a list of
+        [Y, Cb, Cr] 2-D arrays of dtype BLOCKDIFF_DTYPE and shape (bh, bw) ("sad", "sse"), in call order.  Blocks."""
+        n = len(streams_a)
+        if not (len(slots_a) == len(views_a) == len(streams_b) == len(slots_b) == len(views_b) == n):
+            raise ValueError("blockdiff_batch: the six lists differ in length")
+        ca, cb = [as_view(v) for v in views_a], [as_view(v) for v in views_b]
+        dims = [blockdiff_dims(v, k) for v in ca]
+        pitch = max([sum(8 * bw * bh for bw, bh in d) for d in dims], default=0)
+        out = np.zeros((n, pitch), np.uint8)
+        m = max(n, 1)
+        sa, sb = (C.c_void_p * m)(*[s.h for s in streams_a]), (C.c_void_p * m)(*[s.h for s in streams_b])
+        la, lb = (C.c_int * m)(*[int(x) for x in slots_a]), (C.c_int * m)(*[int(x) for x in slots_b])
+        va, vb = (View * m)(*ca), (View * m)(*cb)
+        _check(self.L, self.L.e264hip_blockdiff_batch(self.h, sa, la, va, sb, lb, vb, n, k, out.ctypes.data, pitch), "blockdiff_batch")
+        return [_split_blockdiff(out[j], dims[j]) for j in range(n)]
+
     def event_record(self, idx: int) -> None:
         _check(self.L, self.L.e264hip_event_record(self.h, idx), "event_record")
 
@@ -506,6 +560,23 @@ class Stream:
         out = np.zeros((3, 256), np.uint32)
         _check(self.L, self.L.e264hip_frame_hist(self.h, slot, C.byref(as_view(view)), out.ctypes.data), "frame_hist")
         return out
+
+    def blockdiff(self, slot: int, view=None, other=None, other_slot=None, other_view=None, k: int = 4):
+        """The block difference map (blocks of 1 << k, k = 3 .. 6) of the picture in `slot` against the picture in `other_slot` of stream `other` (default: this
+        stream, the same slot), computed on the device behind everything queued for the streams: [Y, Cb, Cr] 2-D arrays of dtype BLOCKDIFF_DTYPE and shape
+        (bh, bw).  view, other_view: as for diff; default the whole picture of each stream in the reference's layout.  Blocks."""
+        from .digest import frame_view
+        other = self if other is None else other
+        other_slot = slot if other_slot is None else other_slot
+        if view is None:
+            view = frame_view(self.w, self.h_mbs)
+        if other_view is None:
+            other_view = frame_view(other.w, other.h_mbs)
+        cv = as_view(view)
+        dims = blockdiff_dims(cv, k)
+        out = np.zeros(sum(8 * bw * bh for bw, bh in dims), np.uint8)
+        _check(self.L, self.L.e264hip_frame_blockdiff(self.h, slot, C.byref(cv), other.h, other_slot, C.byref(as_view(other_view)), k, out.ctypes.data, out.nbytes), "frame_blockdiff")
+        return _split_blockdiff(out, dims)
 
     def preview(self, slot: int, view=None, k: int = 3):
         """[Y, Cb, Cr] of the picture in `slot` reduced by 1 << k (k = 1, 2, 3) in each direction, computed on the device behind everything queued for the

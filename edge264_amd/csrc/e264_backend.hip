@@ -1004,6 +1004,77 @@ API int e264hip_frame_hist(E264Stream *s, int slot, const E264View *view, E264Hi
 	return e264hip_hist_batch(s->dev, &s, &slot, view, 1, out);
 }
 
+// Block difference maps of n pairs of pictures (include/edge264_hip.h), the pairs checked like e264hip_diff_batch's and the maps carried like
+// e264hip_preview_batch's previews: one kernel on the streams' lane behind everything queued there; ONE page-locked block [jobs | maps] and one device block of the
+// same shape, both from the recycler and back in it behind the call's own serial (jobs sized for n rounded up to 64, maps rounded up to 64 KiB).  In the device
+// block the maps lie back to back, each rounded up to 16 bytes; the kernel writes every record of every map, so nothing is cleared in front.  On the lane, under
+// dev->lock: the table's copy, the kernel, ONE copy of the maps down, the serial.  The wait is for that serial's event, outside the lock; then a memcpy per pair
+// into `out`, whose bytes between the maps are never touched.
+API int e264hip_blockdiff_batch(E264Device *dev, E264Stream *const *streams_a, const int *slots_a, const E264View *views_a,
+	E264Stream *const *streams_b, const int *slots_b, const E264View *views_b, int n, int log2_block, void *out, size_t pitch)
+{
+	if (!dev || n < 0 || n > E264_BLOCKDIFF_MAX_BATCH) return fail(EINVAL, "blockdiff_batch: null device or n outside 0..4096");
+	if (n == 0) return 0;
+	if (!streams_a || !slots_a || !views_a || !streams_b || !slots_b || !views_b || !out) return fail(EINVAL, "blockdiff_batch: null argument");
+	int r;
+	size_t total = 0;
+	for (int i = 0; i < n; i++) {
+		if ((r = check_lane(dev, streams_a, i)) || (r = check_lane(dev, streams_b, i))) return r;
+		if (streams_b[i]->lane != streams_a[0]->lane) return fail(EINVAL, "the streams of a batch must be bound to one compute lane");
+		if (slots_a[i] < 0 || slots_a[i] >= E264_MAX_SLOTS || !streams_a[i]->h_table[slots_a[i]] || slots_b[i] < 0 || slots_b[i] >= E264_MAX_SLOTS || !streams_b[i]->h_table[slots_b[i]])
+			return fail(EINVAL, "blockdiff_batch: slot out of range or not allocated");
+		if ((r = e264hip_blockdiff_check(&views_a[i], streams_a[i]->slot_bytes[slots_a[i]], &views_b[i], streams_b[i]->slot_bytes[slots_b[i]], log2_block))) return r;
+		const size_t b = e264hip_blockdiff_bytes(&views_a[i], log2_block, nullptr); // (> 0: the view has samples and k is in range; < 2^31)
+		if (b > pitch) return fail(EINVAL, "blockdiff_batch: pitch (or cap) smaller than a pair's map");
+		total += (b + 15) & ~(size_t)15;
+		if (total > E264_BLOCKDIFF_MAX_BYTES) return fail(EINVAL, "blockdiff_batch: more than E264_BLOCKDIFF_MAX_BYTES in one call");
+	}
+	if (set_device(dev)) return EIO;
+	const int lane = streams_a[0]->lane;
+	const size_t cap = ((size_t)n + 63) & ~(size_t)63, jobs_bytes = (cap * sizeof(E264BlockDiffJob) + 15) & ~(size_t)15, bytes = jobs_bytes + ((total + 65535) & ~(size_t)65535);
+	uint8_t *h = (uint8_t *)mem_acquire(dev, bytes, true), *d = h ? (uint8_t *)mem_acquire(dev, bytes, false) : nullptr;
+	if (!d) { mem_release(dev, h, bytes, true, 0, 0); return fail(ENOMEM, "blockdiff_batch: job table and maps"); }
+	E264BlockDiffJob *jobs = (E264BlockDiffJob *)h;
+	uint32_t max_chunks = 1;
+	size_t at = jobs_bytes;
+	for (int i = 0; i < n; i++) {
+		jobs[i].base_a = streams_a[i]->h_table[slots_a[i]];
+		jobs[i].slot_bytes_a = streams_a[i]->slot_bytes[slots_a[i]];
+		jobs[i].base_b = streams_b[i]->h_table[slots_b[i]];
+		jobs[i].slot_bytes_b = streams_b[i]->slot_bytes[slots_b[i]];
+		jobs[i].view_a = views_a[i];
+		jobs[i].view_b = views_b[i];
+		jobs[i].dst = d + at;
+		jobs[i].k = (uint32_t)log2_block;
+		jobs[i].chunks = e264_blockdiff_chunks(&views_a[i], log2_block);
+		max_chunks = std::max(max_chunks, jobs[i].chunks);
+		at += (e264hip_blockdiff_bytes(&views_a[i], log2_block, nullptr) + 15) & ~(size_t)15;
+	}
+	uint64_t serial;
+	hipError_t e;
+	{
+		std::lock_guard<std::mutex> g(dev->lock);
+		hipStream_t q = dev->q[lane];
+		e = hipMemcpyAsync(d, h, (size_t)n * sizeof(E264BlockDiffJob), hipMemcpyHostToDevice, q);
+		if (e == hipSuccess) e = e264_launch_blockdiff((const E264BlockDiffJob *)d, n, max_chunks, q);
+		if (e == hipSuccess) e = hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, total, hipMemcpyDeviceToHost, q);
+		serial = next_serial(dev, lane); // (also after an error: whatever was queued reads the two blocks until the lane has passed this point)
+	}
+	r = e == hipSuccess ? serial_wait(dev, serial, lane) : fail(EIO, "blockdiff_batch", e);
+	if (!r)
+		for (int i = 0; i < n; i++)
+			memcpy((uint8_t *)out + (size_t)i * pitch, h + (jobs[i].dst - d), e264hip_blockdiff_bytes(&views_a[i], log2_block, nullptr));
+	mem_release(dev, h, bytes, true, serial, lane);
+	mem_release(dev, d, bytes, false, serial, lane);
+	return r;
+}
+
+API int e264hip_frame_blockdiff(E264Stream *a, int slot_a, const E264View *view_a, E264Stream *b, int slot_b, const E264View *view_b, int log2_block, void *out, size_t cap)
+{
+	if (!a || !b) return fail(EINVAL, "frame_blockdiff: null stream");
+	return e264hip_blockdiff_batch(a->dev, &a, &slot_a, view_a, &b, &slot_b, view_b, 1, log2_block, out, cap);
+}
+
 API int e264hip_packet_upload(E264Device *dev, const void *packet, size_t bytes, E264Packet **out)
 {
 	if (!dev || !out) return fail(EINVAL, "null argument");

@@ -4,6 +4,7 @@
 #include <string.h>
 #include "e264_check.h"
 #include "../../include/edge264_preview.h"
+#include "../../include/edge264_blockdiff.h"
 
 thread_local char e264_err[256];
 int e264_fail(int code, const char *what, const char *detail)
@@ -249,6 +250,29 @@ API int e264hip_diff_check(const E264View *a, size_t slot_bytes_a, const E264Vie
 		if (a->plane[p].width != b->plane[p].width || a->plane[p].height != b->plane[p].height)
 			return fail(EINVAL, "diff_check: the two views' planes differ in size", names[p]);
 	return 0;
+}
+
+// The size of a pair's block difference map at block size 1 << k (include/edge264_hip.h: Y | Cb | Cr, each plane bh x bw records, tight) and its planes' sizes;
+// 0 for what has none.  (At most 3 * 8192 * 8192 records of 8 bytes: below 2^31.)
+API size_t e264hip_blockdiff_bytes(const E264View *v, int log2_block, uint16_t dims[6])
+{
+	size_t bytes = 0;
+	unsigned d[6];
+	if (!v) return 0;
+	for (int p = 0; p < 3; p++) {
+		if (!e264_blockdiff_dims(v->plane[p].width, v->plane[p].height, log2_block, &d[2 * p], &d[2 * p + 1])) return 0;
+		bytes += (size_t)d[2 * p] * d[2 * p + 1] * sizeof(E264BlockDiff);
+	}
+	if (dims)
+		for (int i = 0; i < 6; i++) dims[i] = (uint16_t)d[i];
+	return bytes;
+}
+
+// What a block difference map asks of one pair: what a difference record asks, and a block size the kernel has
+API int e264hip_blockdiff_check(const E264View *a, size_t slot_bytes_a, const E264View *b, size_t slot_bytes_b, int log2_block)
+{
+	if (log2_block < 3 || log2_block > 6) return fail(EINVAL, "blockdiff_check: log2_block is none of 3, 4, 5, 6");
+	return e264hip_diff_check(a, slot_bytes_a, b, slot_bytes_b);
 }
 
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.

@@ -91,4 +91,20 @@ extern "C" uint32_t e264_hist_chunks(const E264View *view);
 // out[i] accumulates the record of job i: the caller clears out (n_jobs records) on `stream` in front.  max_chunks: the largest chunks among the jobs.
 extern "C" hipError_t e264_launch_hist(const E264HistJob *jobs, int n_jobs, uint32_t max_chunks, E264Hist *out, hipStream_t stream);
 
+// e264_blockdiff_kernel (e264_blockdiff.h, e264_blockdiff.hip: a translation unit of its own).  One job = one pair of pictures to compare block by block
+// (blocks of 1 << k, k = 3 .. 6): the two sides as for a diff job, and dst, where the pair's map goes (device memory of e264hip_blockdiff_bytes(view_a, k) bytes,
+// 8-byte aligned: every record of it is written once, nothing outside it).  chunks = e264_blockdiff_chunks(view_a, k).
+struct E264BlockDiffJob {
+	const uint8_t *base_a;
+	uint64_t slot_bytes_a;
+	const uint8_t *base_b;
+	uint64_t slot_bytes_b;
+	E264View view_a, view_b;
+	uint8_t *dst;
+	uint32_t k;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_blockdiff_chunks(const E264View *view, int k);
+extern "C" hipError_t e264_launch_blockdiff(const E264BlockDiffJob *jobs, int n_jobs, uint32_t max_chunks, hipStream_t stream);
+
 #endif

@@ -11,7 +11,7 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
@@ -30,7 +30,12 @@
 // like --digest, and may be combined with it and with --preview.  Without --diff the driver's calls are what they were.  --hist writes s<k>.hist: for every output
 // frame and view the 3072 bytes of the histogram record (include/edge264_hip.h, version 1: 256 little-endian 32-bit counts for Y, then Cb, then Cr), one after the
 // other, computed on the device where the picture lies; bound and ordered like --digest, and may be combined with it, with --preview and with --diff.  Without
-// --hist the driver's calls are what they were.  Prints one JSON line with the throughput.
+// --hist the driver's calls are what they were.  --blockdiff writes s<k>.blockdiff: for every output frame and view from the stream's second frame on, one record
+// with the block difference map (include/edge264_hip.h, version 1: blocks of 1 << K, K = --blockdiff-log2, 3 .. 6, default 4) against the same view of the stream's
+// PREVIOUS output frame -- a 16-byte header (six little-endian 16-bit numbers bw, bh of Y, Cb, Cr, then K as a little-endian 32-bit number) followed by the map,
+// little-endian 32-bit sad, sse per block; a header of zeros but for K and no map where the two frames' dimensions differ -- computed on the device.  Frames are
+// borrowed and one per stream is kept exactly as for --diff (given together, the two share the kept frame); bound and ordered like --digest.  Without
+// --blockdiff the driver's calls are what they were.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -89,6 +94,7 @@ struct Front {
 	int (*frame_diff)(void *, const Edge264Frame *, int, void *, const Edge264Frame *, int, E264DiffRecord *); // (bound with --diff only, as return_frame)
 	void (*return_frame)(void *, void *);
 	int (*frame_hist)(void *, const Edge264Frame *, int, E264HistRecord *); // (bound with --hist only)
+	int (*frame_blockdiff)(void *, const Edge264Frame *, int, void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --blockdiff only, as return_frame)
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -118,7 +124,8 @@ struct Stream {
 	FILE *prev = nullptr;  // --preview: s<k>.preview
 	FILE *dif = nullptr;   // --diff: s<k>.diff
 	FILE *his = nullptr;   // --hist: s<k>.hist
-	Edge264Frame kept;     // --diff: the previous output frame, borrowed (has_kept), until the next one has been compared with it
+	FILE *bdf = nullptr;   // --blockdiff: s<k>.blockdiff
+	Edge264Frame kept;     // --diff, --blockdiff: the previous output frame, borrowed (has_kept), until the next one has been compared with it
 	bool has_kept = false;
 	struct Pkt { void *data; size_t bytes; };
 	std::deque<Pkt> q;     // parsed, not yet submitted (guarded by the queue mutex)
@@ -154,8 +161,9 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir, hist_dir;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir, hist_dir, blockdiff_dir;
 	std::vector<int> devices; // --devices
+	int blockdiff_log2 = 4; // --blockdiff-log2 K: maps of blocks of 1 << K (3 .. 6)
 	int preview_log2 = 3; // --preview-log2 K: previews are reduced by 1 << K (1, 2 or 3)
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
 	int device = 0, repeat = 1, n_threads = 1, loops = 1; // --loops K: every stream is played K times back to back (steady state)
@@ -189,11 +197,13 @@ int main(int argc, char **argv)
 		else if (a == "--preview-log2") preview_log2 = atoi(next().c_str());
 		else if (a == "--diff") diff_dir = next();
 		else if (a == "--hist") hist_dir = next();
+		else if (a == "--blockdiff") blockdiff_dir = next();
+		else if (a == "--blockdiff-log2") blockdiff_log2 = atoi(next().c_str());
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--dump-packets FILE] a.264 ...\n"
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--dump-packets FILE] a.264 ...\n"
 			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
 			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n"
 			"  --preview DIR writes DIR/s<k>.preview: every output frame's and view's preview (Y | Cb | Cr reduced by 1 << K, --preview-log2 K = 1, 2 or 3, default 3),\n"
@@ -202,15 +212,20 @@ int main(int argc, char **argv)
 			"                against the stream's previous output frame (first: - where the planes are equal; the line `size` where the dimensions differ),\n"
 			"                computed on the device; frames are borrowed, one per stream is kept; bound and ordered like --digest\n"
 			"  --hist DIR    writes DIR/s<k>.hist: every output frame's and view's histogram record (256 little-endian 32-bit counts of Y, then Cb, then Cr: 3072 bytes),\n"
-			"                computed on the device; bound and ordered like --digest\n");
+			"                computed on the device; bound and ordered like --digest\n"
+			"  --blockdiff DIR writes DIR/s<k>.blockdiff, one record per output frame and view from the second frame on: a 16-byte header (bw, bh of Y, Cb, Cr as\n"
+			"                little-endian 16-bit numbers, then K as a 32-bit one) and the map of sad, sse per block of 1 << K (--blockdiff-log2 K = 3 .. 6, default 4)\n"
+			"                against the stream's previous output frame, computed on the device; frames are borrowed and kept as for --diff\n");
 		return 2;
 	}
 	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
 	if (!preview_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --preview needs the device (not --parse-only)\n"); return 2; }
 	if (!diff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --diff needs the device (not --parse-only)\n"); return 2; }
 	if (!hist_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --hist needs the device (not --parse-only)\n"); return 2; }
+	if (!blockdiff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --blockdiff needs the device (not --parse-only)\n"); return 2; }
+	if (blockdiff_log2 < 3 || blockdiff_log2 > 6) { fprintf(stderr, "e264_multi: --blockdiff-log2 is 3, 4, 5 or 6\n"); return 2; }
 	if (preview_log2 < 1 || preview_log2 > 3) { fprintf(stderr, "e264_multi: --preview-log2 is 1, 2 or 3\n"); return 2; }
-	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty() || !hist_dir.empty(); // a pass that reads the pictures where they lie
+	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty() || !hist_dir.empty() || !blockdiff_dir.empty(); // a pass that reads the pictures where they lie
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -223,7 +238,7 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
-	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr; F.frame_hist = nullptr;
+	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr; F.frame_hist = nullptr; F.frame_blockdiff = nullptr;
 	if (on_device) { // e264front_frame_digest and e264front_frame_preview live in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
 		const size_t slash = front_path.rfind('/');
 		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
@@ -241,6 +256,7 @@ int main(int argc, char **argv)
 		if (!preview_dir.empty()) bind(dl, "e264front_frame_preview", F.frame_preview);
 		if (!diff_dir.empty()) { bind(dl, "e264front_frame_diff", F.frame_diff); bind(fl, "edge264_return_frame", F.return_frame); }
 		if (!hist_dir.empty()) bind(dl, "e264front_frame_hist", F.frame_hist);
+		if (!blockdiff_dir.empty()) { bind(dl, "e264front_frame_blockdiff", F.frame_blockdiff); bind(fl, "edge264_return_frame", F.return_frame); }
 		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
 		int (*use)(void *, void *) = nullptr;
 		bind(dl, "e264front_digest_use", use);
@@ -301,6 +317,11 @@ int main(int argc, char **argv)
 				t.his = fopen(o.c_str(), "wb");
 				if (!t.his) { perror(o.c_str()); return 2; }
 			}
+			if (!blockdiff_dir.empty()) {
+				std::string o = blockdiff_dir + "/s" + std::to_string(S.size() - 1) + ".blockdiff";
+				t.bdf = fopen(o.c_str(), "wb");
+				if (!t.bdf) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -310,7 +331,7 @@ int main(int argc, char **argv)
 		}
 	FILE *dump = dump_path.empty() ? nullptr : fopen(dump_path.c_str(), "wb");
 
-	// --diff: the kept frame goes back to its decoder (after the next frame's comparison, before a flush, at the stream's end)
+	// --diff, --blockdiff: the kept frame goes back to its decoder (after the next frame's comparison, before a flush, at the stream's end)
 	auto return_kept = [&](Stream &s) {
 		if (s.has_kept) F.return_frame(s.dec, s.kept.return_arg);
 		s.has_kept = false;
@@ -318,7 +339,7 @@ int main(int argc, char **argv)
 	auto drain = [&](Stream &s) {
 		Edge264Frame fr;
 		long n = 0;
-		while (F.get_frame(s.dec, &fr, s.dif ? 1 : 0) == 0) {
+		while (F.get_frame(s.dec, &fr, s.dif || s.bdf ? 1 : 0) == 0) {
 			s.frames++; n++;
 			if (s.out) write_frame(s.out, fr);
 			if (s.dig)
@@ -367,6 +388,31 @@ int main(int argc, char **argv)
 					}
 					fprintf(s.dif, "\n");
 				}
+			}
+			if (s.bdf)
+				for (int v = 0; v < 2 && s.has_kept; v++) { // MVC: the second view's record follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					const int b = 1 << blockdiff_log2;
+					uint8_t hdr[16] = {0};
+					hdr[12] = (uint8_t)blockdiff_log2; // (little-endian, 3 .. 6)
+					if (!(v ? s.kept.samples_mvc : s.kept.samples)[0] || fr.width_Y != s.kept.width_Y || fr.height_Y != s.kept.height_Y || fr.width_C != s.kept.width_C ||
+						fr.height_C != s.kept.height_C) { fwrite(hdr, 1, sizeof(hdr), s.bdf); continue; } // (no map: the header's sizes are zero)
+					// (a bound on the map's size from the frame itself: ceil(w / b) * ceil(h / b) records per plane)
+					std::vector<uint32_t> map(2 * ((size_t)((fr.width_Y + b - 1) / b) * ((fr.height_Y + b - 1) / b) + 2 * (size_t)((fr.width_C + b - 1) / b) * ((fr.height_C + b - 1) / b)));
+					uint16_t dims[6];
+					const int r = F.frame_blockdiff(s.dec, &fr, v, s.dec, &s.kept, v, blockdiff_log2, map.data(), map.size() * 4, dims);
+					if (r) { fprintf(stderr, "e264front_frame_blockdiff: %d (%s)\n", r, H.last_error()); _exit(1); }
+					for (int i = 0; i < 6; i++) { hdr[2 * i] = (uint8_t)dims[i]; hdr[2 * i + 1] = (uint8_t)(dims[i] >> 8); }
+					fwrite(hdr, 1, sizeof(hdr), s.bdf);
+					const size_t words = 2 * ((size_t)dims[0] * dims[1] + (size_t)dims[2] * dims[3] + (size_t)dims[4] * dims[5]);
+					std::vector<uint8_t> le(4 * words); // little-endian whatever the host
+					for (size_t k = 0; k < words; k++) {
+						const uint32_t n = map[k];
+						le[4 * k] = (uint8_t)n; le[4 * k + 1] = (uint8_t)(n >> 8); le[4 * k + 2] = (uint8_t)(n >> 16); le[4 * k + 3] = (uint8_t)(n >> 24);
+					}
+					fwrite(le.data(), 1, le.size(), s.bdf);
+				}
+			if (s.dif || s.bdf) { // the two share the kept frame
 				return_kept(s);
 				s.kept = fr; s.has_kept = true;
 			}
@@ -412,7 +458,7 @@ int main(int argc, char **argv)
 				const long long t_dr = now_ns();
 				const long n_out = drain(s);
 				ns_drain += now_ns() - t_dr;
-				// --diff: at the end of a sequence and at a change of SPS the decoder wants EVERY frame back before it goes on (bump_all_frames,
+				// --diff, --blockdiff: at the end of a sequence and at a change of SPS the decoder wants EVERY frame back before it goes on (bump_all_frames,
 				// src/edge264_headers.c:97-104), the kept one too: the comparison starts again with the next sequence's first frame
 				if (n_out == 0 && s.has_kept) { return_kept(s); continue; }
 				if (n_out == 0) {
@@ -426,7 +472,7 @@ int main(int argc, char **argv)
 						std::lock_guard<std::mutex> lk(mu);
 						if (!s.q.empty()) return BLOCKED;
 					}
-					return_kept(s); // (--diff: nothing of this decoder stays borrowed over a flush; the comparison starts again with the next frame)
+					return_kept(s); // (--diff, --blockdiff: nothing of this decoder stays borrowed over a flush; the comparison starts again with the next frame)
 					F.flush(s.dec);
 					s.just_flushed = true;
 					stuck_flushes++;
@@ -612,6 +658,7 @@ int main(int argc, char **argv)
 		if (s.dig) fclose(s.dig);
 		if (s.prev) fclose(s.prev);
 		if (s.dif) fclose(s.dif);
+		if (s.bdf) fclose(s.bdf);
 		if (s.his) fclose(s.his);
 		F.free_dec(&s.dec);
 	}

@@ -223,6 +223,54 @@ typedef struct { uint32_t bin[3][256]; } E264Hist;   /* Y, Cb, Cr: 3072 bytes */
 int  e264hip_frame_hist(E264Stream *s, int slot, const E264View *view, E264Hist *out);
 int  e264hip_hist_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, E264Hist *out);
 
+/* ---- WHERE two decoded pictures differ: the per-block difference map, computed on the device ------------- */
+/* The difference record says how two pictures relate as a whole and names one sample; the map says where they differ and by how much, block by
+ * block: which macroblocks of a picture whose digest did not match went wrong, motion masks and regional freeze detection (a picture that stands
+ * still but for a clock or a ticker), regional PSNR of two renditions, regions of interest for a transcode or inference stage -- without reading
+ * either picture back.  The reference has no counterpart (include/edge264_blockdiff.h's e264_blockdiff_plane does the same arithmetic on two
+ * Edge264Frames' planes on the host).
+ *
+ * THE BLOCK DIFFERENCE MAP, version E264_BLOCKDIFF_VERSION.  k = log2_block in {3, 4, 5, 6}, b = 1 << k.  For plane p of view A and of view B, both
+ * w x h samples:
+ *     bw = (w + b - 1) >> k          bh = (h + b - 1) >> k
+ *     record (Y, X) covers the samples y in [b Y, min(b Y + b, h)), x in [b X, min(b X + b, w)):  sad = sum |a - b|,  sse = sum (a - b)^2
+ * Samples outside the view do not count: there is no clamping and no replication, a block at the right or bottom edge simply has fewer samples.
+ * One pair's map is Y | Cb | Cr, each plane row-major bh x bw records, tight.  The three planes use the same b independently, each over its own
+ * (cropped) view, as the preview does, so the result stays 4:2:0: a chroma block of b covers the area of a luma block of 2 b.
+ * Everything is exact: a block has at most 64 x 64 = 4096 samples, so sad <= 4096 * 255 < 2^21 and sse <= 4096 * 255^2 = 266 342 400 < 2^32.
+ * For every plane, the sum of sad over the map is E264PlaneDiff.sad of the same pair and the sum of sse its sse; and
+ * sad == 0 <=> sse == 0 <=> the block's samples are equal.
+ *
+ * e264hip_blockdiff_bytes (host only): the map's size, and in dims (may be NULL) bw, bh of Y, Cb, Cr; 0 for a null view, k outside 3..6 or a plane
+ *   without samples.
+ * e264hip_blockdiff_batch: the map of views_a[i] of slot slots_a[i] of streams_a[i] against views_b[i] of slot slots_b[i] of streams_b[i] at
+ *   out + i * pitch; only its e264hip_blockdiff_bytes bytes there are written, the rest of a pitch is left as it was.  e264hip_frame_blockdiff is the
+ *   batch of one with pitch = cap.  Both BLOCK until `out` (ordinary host memory) is filled.  A and B may be different streams, the same stream, even
+ *   the same slot and view (every record is then zero).
+ * Ordering: one kernel per call, whatever n, queued on the streams' compute lane behind everything queued there -- a map asked for right after
+ *   e264hip_frame_submit, e264hip_submit_batch*, e264hip_frame_fill or e264hip_frame_upload, with no wait between, sees that work's result.  All
+ *   streams of a call, on both sides, belong to `dev` and share one lane, as for a submission (else EINVAL); a stream may appear more than once (the
+ *   pass only reads).  The call waits for its own event, never for the device.
+ * Lifetime: the call marks the lane as a fill does, so a slot freed while it runs stays parked behind it (e264hip_frame_free never hands memory
+ *   back under a kernel); the caller drives the streams, as for a submission.
+ * Errors: EINVAL (and nothing is queued, `out` is untouched) for a null pointer, n < 0, n > E264_BLOCKDIFF_MAX_BATCH, k outside 3..6, a slot out of
+ *   range or not allocated, streams of two devices or two lanes, a view e264hip_view_check refuses for its own slot's size (either side), plane p of A
+ *   and of B differing in width or height for any p, pitch or cap smaller than a pair's map, more than E264_BLOCKDIFF_MAX_BYTES in one call;
+ *   e264hip_last_error() names the cause.  n == 0 returns 0.
+ * e264hip_blockdiff_check (host only): e264hip_diff_check plus the range of k -- what the two calls ask of one pair; 0 or EINVAL with a text. */
+typedef struct { uint32_t sad, sse; } E264BlockDiff;   /* 8 bytes: sum |a - b|, sum (a - b)^2 over the block's samples */
+#define E264_BLOCKDIFF_VERSION 1
+#define E264_BLOCKDIFF_MAX_BATCH 4096
+#define E264_BLOCKDIFF_MAX_BYTES (1u << 28)   /* of one call: the sum of the pairs' maps, each rounded up to 16 */
+size_t e264hip_blockdiff_bytes(const E264View *v, int log2_block, uint16_t dims[6]);
+int  e264hip_blockdiff_check(const E264View *view_a, size_t slot_bytes_a, const E264View *view_b, size_t slot_bytes_b, int log2_block);
+int  e264hip_frame_blockdiff(E264Stream *a, int slot_a, const E264View *view_a,
+                             E264Stream *b, int slot_b, const E264View *view_b, int log2_block, void *out, size_t cap);
+int  e264hip_blockdiff_batch(E264Device *dev,
+                             E264Stream *const *streams_a, const int *slots_a, const E264View *views_a,
+                             E264Stream *const *streams_b, const int *slots_b, const E264View *views_b,
+                             int n, int log2_block, void *out, size_t pitch);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
