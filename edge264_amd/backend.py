@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import packet as P
+from .blockstat import BLOCKSTAT_DTYPE, split_map as _split_blockstat  # E264BlockStat as numpy sees it (16 bytes) and a map's bytes as three 2-D arrays of it
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E264_HIP_LIB") or os.path.join(HERE, "libedge264_hip.so")  # E264_HIP_LIB: A/B builds (csrc/Makefile `variant`)
@@ -45,6 +46,8 @@ BLOCKDIFF_MAX_BATCH = 4096
 BLOCKDIFF_MAX_BYTES = 1 << 28
 # E264BlockDiff as numpy sees it: a plane's map is an array of shape (bh, bw) of this record (8 bytes)
 BLOCKDIFF_DTYPE = np.dtype([("sad", "<u4"), ("sse", "<u4")])
+BLOCKSTAT_MAX_BATCH = 4096
+BLOCKSTAT_MAX_BYTES = 1 << 28
 HIST_MAX_BATCH = 4096  # E264Hist as numpy sees it: uint32 of shape (n, 3, 256) -- pictures, then Y, Cb, Cr, then the sample value
 
 
@@ -127,6 +130,10 @@ def load_library():
         "e264hip_blockdiff_check": (i, [C.POINTER(View), sz, C.POINTER(View), sz, i]),
         "e264hip_frame_blockdiff": (i, [vp, i, C.POINTER(View), vp, i, C.POINTER(View), i, vp, sz]),
         "e264hip_blockdiff_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, i, vp, sz]),
+        "e264hip_blockstat_bytes": (sz, [C.POINTER(View), i, C.POINTER(C.c_uint16)]),
+        "e264hip_blockstat_check": (i, [C.POINTER(View), sz, i]),
+        "e264hip_frame_blockstat": (i, [vp, i, C.POINTER(View), i, vp, sz]),
+        "e264hip_blockstat_batch": (i, [vp, C.POINTER(vp), C.POINTER(i), C.POINTER(View), i, i, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the library does not export the header's symbol
@@ -156,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "e264hip_diff_check", "e264hip_frame_diff", "e264hip_diff_batch",
     "e264hip_frame_hist", "e264hip_hist_batch",
     "e264hip_blockdiff_bytes", "e264hip_blockdiff_check", "e264hip_frame_blockdiff", "e264hip_blockdiff_batch",
+    "e264hip_blockstat_bytes", "e264hip_blockstat_check", "e264hip_frame_blockstat", "e264hip_blockstat_batch",
 ]
 
 # slots of e264hip_launch_counts (E264_LC_NAMES in include/edge264_hip.h): "n_cus" is the device's compute-unit count, every
@@ -214,6 +222,24 @@ def _split_blockdiff(buf: np.ndarray, dims):
         out.append(buf[at:at + n].view(BLOCKDIFF_DTYPE).reshape(bh, bw))
         at += n
     return out
+
+
+def blockstat_dims(view, k: int):
+    """[(bw, bh)] of Y, Cb, Cr of a view's block statistics map at block size 1 << k, from the library (host only); raises for what has none"""
+    d = (C.c_uint16 * 6)()
+    if not load_library().e264hip_blockstat_bytes(C.byref(as_view(view)), k, d):
+        raise ValueError("blockstat: k is 3, 4, 5 or 6 and every plane of the view has samples")
+    return [(int(d[2 * p]), int(d[2 * p + 1])) for p in range(3)]
+
+
+def blockstat_bytes(view, k: int) -> int:
+    """e264hip_blockstat_bytes: the bytes of a view's block statistics map at block size 1 << k (Y | Cb | Cr, each plane tight); 0 for what has none.  Host only."""
+    return int(load_library().e264hip_blockstat_bytes(C.byref(as_view(view)) if view is not None else None, k, None))
+
+
+def blockstat_check(view, slot_bytes: int, k: int) -> int:
+    """e264hip_blockstat_check: 0, or EINVAL (last_error() names the cause) for a view or a block size a map cannot be made of.  Host only."""
+    return int(load_library().e264hip_blockstat_check(C.byref(as_view(view)), slot_bytes, k))
 
 
 def _split_preview(buf: np.ndarray, dims):
@@ -445,6 +471,24 @@ class Device:
         _check(self.L, self.L.e264hip_blockdiff_batch(self.h, sa, la, va, sb, lb, vb, n, k, out.ctypes.data, pitch), "blockdiff_batch")
         return [_split_blockdiff(out[j], dims[j]) for j in range(n)]
 
+    def blockstat_batch(self, streams, slots, views, k: int = 4):
+        """The block statistics maps (include/edge264_hip.h, version 1: blocks of 1 << k, k = 3 .. 6) of views[i] of slot slots[i] of streams[i], computed on the
+        device behind everything queued on the streams' lane, in one kernel: a list of [Y, Cb, Cr] 2-D arrays of dtype BLOCKSTAT_DTYPE and shape (bh, bw)
+        ("sum", "sumsq", "gh", "gv"), in call order.  Blocks."""
+        n = len(streams)
+        if not (len(slots) == len(views) == n):
+            raise ValueError("blockstat_batch: streams, slots and views differ in length")
+        cv = [as_view(v) for v in views]
+        dims = [blockstat_dims(v, k) for v in cv]
+        pitch = max([sum(16 * bw * bh for bw, bh in d) for d in dims], default=0)
+        out = np.zeros((n, pitch), np.uint8)
+        m = max(n, 1)
+        sa = (C.c_void_p * m)(*[s.h for s in streams])
+        la = (C.c_int * m)(*[int(x) for x in slots])
+        va = (View * m)(*cv)
+        _check(self.L, self.L.e264hip_blockstat_batch(self.h, sa, la, va, n, k, out.ctypes.data, pitch), "blockstat_batch")
+        return [_split_blockstat(out[j], dims[j]) for j in range(n)]
+
     def event_record(self, idx: int) -> None:
         _check(self.L, self.L.e264hip_event_record(self.h, idx), "event_record")
 
@@ -577,6 +621,18 @@ class Stream:
         out = np.zeros(sum(8 * bw * bh for bw, bh in dims), np.uint8)
         _check(self.L, self.L.e264hip_frame_blockdiff(self.h, slot, C.byref(cv), other.h, other_slot, C.byref(as_view(other_view)), k, out.ctypes.data, out.nbytes), "frame_blockdiff")
         return _split_blockdiff(out, dims)
+
+    def blockstat(self, slot: int, view=None, k: int = 4):
+        """The block statistics map (blocks of 1 << k, k = 3 .. 6) of the picture in `slot`, computed on the device behind everything queued for the stream:
+        [Y, Cb, Cr] 2-D arrays of dtype BLOCKSTAT_DTYPE and shape (bh, bw).  view: as for digest; default the whole picture in the reference's layout.  Blocks."""
+        from .digest import frame_view
+        if view is None:
+            view = frame_view(self.w, self.h_mbs)
+        cv = as_view(view)
+        dims = blockstat_dims(cv, k)
+        out = np.zeros(sum(16 * bw * bh for bw, bh in dims), np.uint8)
+        _check(self.L, self.L.e264hip_frame_blockstat(self.h, slot, C.byref(cv), k, out.ctypes.data, out.nbytes), "frame_blockstat")
+        return _split_blockstat(out, dims)
 
     def preview(self, slot: int, view=None, k: int = 3):
         """[Y, Cb, Cr] of the picture in `slot` reduced by 1 << k (k = 1, 2, 3) in each direction, computed on the device behind everything queued for the

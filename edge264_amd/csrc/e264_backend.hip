@@ -1075,6 +1075,71 @@ API int e264hip_frame_blockdiff(E264Stream *a, int slot_a, const E264View *view_
 	return e264hip_blockdiff_batch(a->dev, &a, &slot_a, view_a, &b, &slot_b, view_b, 1, log2_block, out, cap);
 }
 
+// Block statistics maps of n pictures (include/edge264_hip.h), the pictures checked like e264hip_hist_batch's and the maps carried like
+// e264hip_blockdiff_batch's: one kernel on the streams' lane behind everything queued there; ONE page-locked block [jobs | maps] and one device block of the
+// same shape, both from the recycler and back in it behind the call's own serial (jobs sized for n rounded up to 64, maps rounded up to 64 KiB).  In the device
+// block the maps lie back to back (a record is 16 bytes, so every map is 16-byte aligned); the kernel writes every record of every map, so nothing is cleared in
+// front.  On the lane, under dev->lock: the table's copy, the kernel, ONE copy of the maps down, the serial.  The wait is for that serial's event, outside the
+// lock; then a memcpy per picture into `out`, whose bytes between the maps are never touched.
+API int e264hip_blockstat_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views, int n, int log2_block, void *out, size_t pitch)
+{
+	if (!dev || n < 0 || n > E264_BLOCKSTAT_MAX_BATCH) return fail(EINVAL, "blockstat_batch: null device or n outside 0..4096");
+	if (n == 0) return 0;
+	if (!streams || !slots || !views || !out) return fail(EINVAL, "blockstat_batch: null argument");
+	int r;
+	size_t total = 0;
+	for (int i = 0; i < n; i++) {
+		if ((r = check_lane(dev, streams, i))) return r;
+		if (slots[i] < 0 || slots[i] >= E264_MAX_SLOTS || !streams[i]->h_table[slots[i]]) return fail(EINVAL, "blockstat_batch: slot out of range or not allocated");
+		if ((r = e264hip_blockstat_check(&views[i], streams[i]->slot_bytes[slots[i]], log2_block))) return r;
+		const size_t b = e264hip_blockstat_bytes(&views[i], log2_block, nullptr); // (> 0: the view has samples and k is in range; a multiple of 16)
+		if (b > pitch) return fail(EINVAL, "blockstat_batch: pitch (or cap) smaller than a picture's map");
+		total += b;
+		if (total > E264_BLOCKSTAT_MAX_BYTES) return fail(EINVAL, "blockstat_batch: more than E264_BLOCKSTAT_MAX_BYTES in one call");
+	}
+	if (set_device(dev)) return EIO;
+	const int lane = streams[0]->lane;
+	const size_t cap = ((size_t)n + 63) & ~(size_t)63, jobs_bytes = (cap * sizeof(E264BlockStatJob) + 15) & ~(size_t)15, bytes = jobs_bytes + ((total + 65535) & ~(size_t)65535);
+	uint8_t *h = (uint8_t *)mem_acquire(dev, bytes, true), *d = h ? (uint8_t *)mem_acquire(dev, bytes, false) : nullptr;
+	if (!d) { mem_release(dev, h, bytes, true, 0, 0); return fail(ENOMEM, "blockstat_batch: job table and maps"); }
+	E264BlockStatJob *jobs = (E264BlockStatJob *)h;
+	uint32_t max_chunks = 1;
+	size_t at = jobs_bytes;
+	for (int i = 0; i < n; i++) {
+		jobs[i].base = streams[i]->h_table[slots[i]];
+		jobs[i].slot_bytes = streams[i]->slot_bytes[slots[i]];
+		jobs[i].view = views[i];
+		jobs[i].dst = d + at;
+		jobs[i].k = (uint32_t)log2_block;
+		jobs[i].chunks = e264_blockstat_chunks(&views[i], log2_block);
+		max_chunks = std::max(max_chunks, jobs[i].chunks);
+		at += e264hip_blockstat_bytes(&views[i], log2_block, nullptr);
+	}
+	uint64_t serial;
+	hipError_t e;
+	{
+		std::lock_guard<std::mutex> g(dev->lock);
+		hipStream_t q = dev->q[lane];
+		e = hipMemcpyAsync(d, h, (size_t)n * sizeof(E264BlockStatJob), hipMemcpyHostToDevice, q);
+		if (e == hipSuccess) e = e264_launch_blockstat((const E264BlockStatJob *)d, n, max_chunks, q);
+		if (e == hipSuccess) e = hipMemcpyAsync(h + jobs_bytes, d + jobs_bytes, total, hipMemcpyDeviceToHost, q);
+		serial = next_serial(dev, lane); // (also after an error: whatever was queued reads the two blocks until the lane has passed this point)
+	}
+	r = e == hipSuccess ? serial_wait(dev, serial, lane) : fail(EIO, "blockstat_batch", e);
+	if (!r)
+		for (int i = 0; i < n; i++)
+			memcpy((uint8_t *)out + (size_t)i * pitch, h + (jobs[i].dst - d), e264hip_blockstat_bytes(&views[i], log2_block, nullptr));
+	mem_release(dev, h, bytes, true, serial, lane);
+	mem_release(dev, d, bytes, false, serial, lane);
+	return r;
+}
+
+API int e264hip_frame_blockstat(E264Stream *s, int slot, const E264View *view, int log2_block, void *out, size_t cap)
+{
+	if (!s) return fail(EINVAL, "frame_blockstat: null stream");
+	return e264hip_blockstat_batch(s->dev, &s, &slot, view, 1, log2_block, out, cap);
+}
+
 API int e264hip_packet_upload(E264Device *dev, const void *packet, size_t bytes, E264Packet **out)
 {
 	if (!dev || !out) return fail(EINVAL, "null argument");

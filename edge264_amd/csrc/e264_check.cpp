@@ -5,6 +5,7 @@
 #include "e264_check.h"
 #include "../../include/edge264_preview.h"
 #include "../../include/edge264_blockdiff.h"
+#include "../../include/edge264_blockstat.h"
 
 thread_local char e264_err[256];
 int e264_fail(int code, const char *what, const char *detail)
@@ -273,6 +274,29 @@ API int e264hip_blockdiff_check(const E264View *a, size_t slot_bytes_a, const E2
 {
 	if (log2_block < 3 || log2_block > 6) return fail(EINVAL, "blockdiff_check: log2_block is none of 3, 4, 5, 6");
 	return e264hip_diff_check(a, slot_bytes_a, b, slot_bytes_b);
+}
+
+// The size of a picture's block statistics map at block size 1 << k (include/edge264_hip.h: Y | Cb | Cr, each plane bh x bw records, tight) and its planes'
+// sizes; 0 for what has none.  (At most 3 * 8192 * 8192 records of 16 bytes: below 2^32.)
+API size_t e264hip_blockstat_bytes(const E264View *v, int log2_block, uint16_t dims[6])
+{
+	size_t bytes = 0;
+	unsigned d[6];
+	if (!v) return 0;
+	for (int p = 0; p < 3; p++) {
+		if (!e264_blockstat_dims(v->plane[p].width, v->plane[p].height, log2_block, &d[2 * p], &d[2 * p + 1])) return 0;
+		bytes += (size_t)d[2 * p] * d[2 * p + 1] * sizeof(E264BlockStat);
+	}
+	if (dims)
+		for (int i = 0; i < 6; i++) dims[i] = (uint16_t)d[i];
+	return bytes;
+}
+
+// What a block statistics map asks of one picture: what every pass asks of a view, and a block size the kernel has
+API int e264hip_blockstat_check(const E264View *view, size_t slot_bytes, int log2_block)
+{
+	if (log2_block < 3 || log2_block > 6) return fail(EINVAL, "blockstat_check: log2_block is none of 3, 4, 5, 6");
+	return e264hip_view_check(view, slot_bytes);
 }
 
 // The wire form (include/edge264_compact.h) for callers that do not compile C: the Python tools, a binding in another language.

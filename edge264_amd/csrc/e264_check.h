@@ -1,6 +1,6 @@
 // e264_check.h -- the gate in front of the GPU: what a command packet must satisfy before a kernel may read it.  Host code only (plain C++17, no HIP): it reads
 // hostile bytes, so tools/sanitize/kernel_fuzz.py builds and runs it under AddressSanitizer.  e264_check.cpp also holds the entry points of include/edge264_hip.h
-// that need no device (e264hip_packet_check, e264hip_packet_compact_bound, e264hip_packet_compact, e264hip_packet_compact2_bound, e264hip_packet_compact2, e264hip_packet_fold_bound, e264hip_packet_fold, e264hip_packet_expand, e264hip_view_check, e264hip_preview_bytes, e264hip_diff_check, e264hip_blockdiff_bytes, e264hip_blockdiff_check, e264hip_last_error).
+// that need no device (e264hip_packet_check, e264hip_packet_compact_bound, e264hip_packet_compact, e264hip_packet_compact2_bound, e264hip_packet_compact2, e264hip_packet_fold_bound, e264hip_packet_fold, e264hip_packet_expand, e264hip_view_check, e264hip_preview_bytes, e264hip_diff_check, e264hip_blockdiff_bytes, e264hip_blockdiff_check, e264hip_blockstat_bytes, e264hip_blockstat_check, e264hip_last_error).
 #ifndef E264_CHECK_H
 #define E264_CHECK_H
 #include "../../include/edge264_hip.h"

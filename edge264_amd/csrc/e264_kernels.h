@@ -107,4 +107,19 @@ struct E264BlockDiffJob {
 extern "C" uint32_t e264_blockdiff_chunks(const E264View *view, int k);
 extern "C" hipError_t e264_launch_blockdiff(const E264BlockDiffJob *jobs, int n_jobs, uint32_t max_chunks, hipStream_t stream);
 
+// e264_blockstat_kernel (e264_blockstat.h, e264_blockstat.hip: a translation unit of its own).  One job = one picture to describe block by block (blocks of
+// 1 << k, k = 3 .. 6): slot, size and view as for a digest job -- no byte outside [base, base + slot_bytes) is read -- and dst, where the picture's map goes
+// (device memory of e264hip_blockstat_bytes(view, k) bytes, 16-byte aligned: every record of it is written once, nothing outside it).
+// chunks = e264_blockstat_chunks(view, k).
+struct E264BlockStatJob {
+	const uint8_t *base;
+	uint64_t slot_bytes;
+	E264View view;
+	uint8_t *dst;
+	uint32_t k;
+	uint32_t chunks;
+};
+extern "C" uint32_t e264_blockstat_chunks(const E264View *view, int k);
+extern "C" hipError_t e264_launch_blockstat(const E264BlockStatJob *jobs, int n_jobs, uint32_t max_chunks, hipStream_t stream);
+
 #endif

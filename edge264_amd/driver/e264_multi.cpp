@@ -11,7 +11,7 @@
 // picture -- an I picture with CABAC -- and 64 threads parsed 4.7 k pictures/s where one parses 400).
 //
 //   e264_multi --front <libedge264_hipfront.so> --hip <libedge264_hip.so> [--device N | --devices 0,1,...] [--repeat R]
-//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
+//              [--threads T] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--blockstat DIR [--blockstat-log2 K]] [--dump-packets FILE] [--parse-only] [--no-download] a.264 b.264 ...
 //
 // --devices: decoder k lives on GPU devices[k mod N] (streams are independent: no traffic between GPUs); every
 // GPU has its own submitter thread and its own batches.
@@ -35,7 +35,11 @@
 // PREVIOUS output frame -- a 16-byte header (six little-endian 16-bit numbers bw, bh of Y, Cb, Cr, then K as a little-endian 32-bit number) followed by the map,
 // little-endian 32-bit sad, sse per block; a header of zeros but for K and no map where the two frames' dimensions differ -- computed on the device.  Frames are
 // borrowed and one per stream is kept exactly as for --diff (given together, the two share the kept frame); bound and ordered like --digest.  Without
-// --blockdiff the driver's calls are what they were.  Prints one JSON line with the throughput.
+// --blockdiff the driver's calls are what they were.  --blockstat writes s<k>.blockstat: for every output frame and view, from the first on, one record with the
+// block statistics map (include/edge264_hip.h, version 1: blocks of 1 << K, K = --blockstat-log2, 3 .. 6, default 4) -- a 16-byte header (six little-endian
+// 16-bit numbers bw, bh of Y, Cb, Cr, then K as a little-endian 32-bit number) followed by the map, little-endian 32-bit sum, sumsq, gh, gv per block --
+// computed on the device where the picture lies; bound and ordered like --digest, and may be combined with the other passes.  Without --blockstat the driver's
+// calls are what they were.  Prints one JSON line with the throughput.
 #include <cerrno>
 #include <chrono>
 #include <cstdint>
@@ -95,6 +99,7 @@ struct Front {
 	void (*return_frame)(void *, void *);
 	int (*frame_hist)(void *, const Edge264Frame *, int, E264HistRecord *); // (bound with --hist only)
 	int (*frame_blockdiff)(void *, const Edge264Frame *, int, void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --blockdiff only, as return_frame)
+	int (*frame_blockstat)(void *, const Edge264Frame *, int, int, void *, size_t, uint16_t *); // (bound with --blockstat only)
 };
 struct Hip {
 	int (*submit_batch_host)(void *, void **, const void **, const size_t *, int, int);
@@ -125,6 +130,7 @@ struct Stream {
 	FILE *dif = nullptr;   // --diff: s<k>.diff
 	FILE *his = nullptr;   // --hist: s<k>.hist
 	FILE *bdf = nullptr;   // --blockdiff: s<k>.blockdiff
+	FILE *bst = nullptr;   // --blockstat: s<k>.blockstat
 	Edge264Frame kept;     // --diff, --blockdiff: the previous output frame, borrowed (has_kept), until the next one has been compared with it
 	bool has_kept = false;
 	struct Pkt { void *data; size_t bytes; };
@@ -161,9 +167,10 @@ int main(int argc, char **argv)
 {
 	signal(SIGSEGV, on_crash);
 	signal(SIGBUS, on_crash);
-	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir, hist_dir, blockdiff_dir;
+	std::string front_path, hip_path, out_dir, dump_path, digest_dir, preview_dir, diff_dir, hist_dir, blockdiff_dir, blockstat_dir;
 	std::vector<int> devices; // --devices
 	int blockdiff_log2 = 4; // --blockdiff-log2 K: maps of blocks of 1 << K (3 .. 6)
+	int blockstat_log2 = 4; // --blockstat-log2 K: maps of blocks of 1 << K (3 .. 6)
 	int preview_log2 = 3; // --preview-log2 K: previews are reduced by 1 << K (1, 2 or 3)
 	int ahead = 3; // --ahead K: pictures a decoder may be parsed ahead of the device
 	int device = 0, repeat = 1, n_threads = 1, loops = 1; // --loops K: every stream is played K times back to back (steady state)
@@ -199,11 +206,13 @@ int main(int argc, char **argv)
 		else if (a == "--hist") hist_dir = next();
 		else if (a == "--blockdiff") blockdiff_dir = next();
 		else if (a == "--blockdiff-log2") blockdiff_log2 = atoi(next().c_str());
+		else if (a == "--blockstat") blockstat_dir = next();
+		else if (a == "--blockstat-log2") blockstat_log2 = atoi(next().c_str());
 		else if (a == "--dump-packets") dump_path = next();
 		else files.push_back(a);
 	}
 	if (front_path.empty() || hip_path.empty() || files.empty()) {
-		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--dump-packets FILE] a.264 ...\n"
+		fprintf(stderr, "usage: e264_multi --front libedge264_hipfront.so --hip libedge264_hip.so [--device N] [--repeat R] [--out DIR] [--digest DIR] [--preview DIR [--preview-log2 K]] [--diff DIR] [--hist DIR] [--blockdiff DIR [--blockdiff-log2 K]] [--blockstat DIR [--blockstat-log2 K]] [--dump-packets FILE] a.264 ...\n"
 			"  --digest DIR  a verification mode: writes DIR/s<k>.digest, one line per output frame and view with the picture's digest (Y Cb Cr, 16 hex digits each)\n"
 			"                computed on the device; works with --no-download; blocks per frame, so the frame rate it prints is not the product's\n"
 			"  --preview DIR writes DIR/s<k>.preview: every output frame's and view's preview (Y | Cb | Cr reduced by 1 << K, --preview-log2 K = 1, 2 or 3, default 3),\n"
@@ -215,7 +224,10 @@ int main(int argc, char **argv)
 			"                computed on the device; bound and ordered like --digest\n"
 			"  --blockdiff DIR writes DIR/s<k>.blockdiff, one record per output frame and view from the second frame on: a 16-byte header (bw, bh of Y, Cb, Cr as\n"
 			"                little-endian 16-bit numbers, then K as a 32-bit one) and the map of sad, sse per block of 1 << K (--blockdiff-log2 K = 3 .. 6, default 4)\n"
-			"                against the stream's previous output frame, computed on the device; frames are borrowed and kept as for --diff\n");
+			"                against the stream's previous output frame, computed on the device; frames are borrowed and kept as for --diff\n"
+			"  --blockstat DIR writes DIR/s<k>.blockstat, one record per output frame and view: a 16-byte header (bw, bh of Y, Cb, Cr as little-endian 16-bit\n"
+			"                numbers, then K as a 32-bit one) and the map of sum, sumsq, gh, gv per block of 1 << K (--blockstat-log2 K = 3 .. 6, default 4),\n"
+			"                computed on the device; bound and ordered like --digest\n");
 		return 2;
 	}
 	if (!digest_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --digest needs the device (not --parse-only)\n"); return 2; }
@@ -223,9 +235,11 @@ int main(int argc, char **argv)
 	if (!diff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --diff needs the device (not --parse-only)\n"); return 2; }
 	if (!hist_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --hist needs the device (not --parse-only)\n"); return 2; }
 	if (!blockdiff_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --blockdiff needs the device (not --parse-only)\n"); return 2; }
+	if (!blockstat_dir.empty() && parse_only) { fprintf(stderr, "e264_multi: --blockstat needs the device (not --parse-only)\n"); return 2; }
+	if (blockstat_log2 < 3 || blockstat_log2 > 6) { fprintf(stderr, "e264_multi: --blockstat-log2 is 3, 4, 5 or 6\n"); return 2; }
 	if (blockdiff_log2 < 3 || blockdiff_log2 > 6) { fprintf(stderr, "e264_multi: --blockdiff-log2 is 3, 4, 5 or 6\n"); return 2; }
 	if (preview_log2 < 1 || preview_log2 > 3) { fprintf(stderr, "e264_multi: --preview-log2 is 1, 2 or 3\n"); return 2; }
-	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty() || !hist_dir.empty() || !blockdiff_dir.empty(); // a pass that reads the pictures where they lie
+	const bool on_device = !digest_dir.empty() || !preview_dir.empty() || !diff_dir.empty() || !hist_dir.empty() || !blockdiff_dir.empty() || !blockstat_dir.empty(); // a pass that reads the pictures where they lie
 	setenv("E264_HIP_LIB", hip_path.c_str(), 1); // the front end binds the same back-end library
 	void *hl = dlopen(hip_path.c_str(), RTLD_NOW | RTLD_GLOBAL);
 	if (!hl && !parse_only) { fprintf(stderr, "e264_multi: %s\n", dlerror()); return 2; } // no back end, no decoding: there is no CPU fallback
@@ -238,7 +252,7 @@ int main(int argc, char **argv)
 	bind(fl, "e264front_set_pinned", F.set_pinned);
 	bind(fl, "e264front_take_packet", F.take_packet); bind(fl, "e264front_free_packet", F.free_packet);
 	bind(fl, "e264front_stream", F.stream); bind(fl, "e264front_device", F.device); bind(fl, "e264front_device_of", F.device_of);
-	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr; F.frame_hist = nullptr; F.frame_blockdiff = nullptr;
+	F.frame_digest = nullptr; F.frame_preview = nullptr; F.frame_diff = nullptr; F.return_frame = nullptr; F.frame_hist = nullptr; F.frame_blockdiff = nullptr; F.frame_blockstat = nullptr;
 	if (on_device) { // e264front_frame_digest and e264front_frame_preview live in libedge264_frontdigest.so (edge264_amd/frontend/front_digest.c): beside the front library, else beside this program
 		const size_t slash = front_path.rfind('/');
 		std::string dpath = (slash == std::string::npos ? std::string(".") : front_path.substr(0, slash)) + "/libedge264_frontdigest.so";
@@ -257,6 +271,7 @@ int main(int argc, char **argv)
 		if (!diff_dir.empty()) { bind(dl, "e264front_frame_diff", F.frame_diff); bind(fl, "edge264_return_frame", F.return_frame); }
 		if (!hist_dir.empty()) bind(dl, "e264front_frame_hist", F.frame_hist);
 		if (!blockdiff_dir.empty()) { bind(dl, "e264front_frame_blockdiff", F.frame_blockdiff); bind(fl, "edge264_return_frame", F.return_frame); }
+		if (!blockstat_dir.empty()) bind(dl, "e264front_frame_blockstat", F.frame_blockstat);
 		// it works on THESE two libraries, wherever they lie: the decoders below come from this instance of the front library
 		int (*use)(void *, void *) = nullptr;
 		bind(dl, "e264front_digest_use", use);
@@ -322,6 +337,11 @@ int main(int argc, char **argv)
 				t.bdf = fopen(o.c_str(), "wb");
 				if (!t.bdf) { perror(o.c_str()); return 2; }
 			}
+			if (!blockstat_dir.empty()) {
+				std::string o = blockstat_dir + "/s" + std::to_string(S.size() - 1) + ".blockstat";
+				t.bst = fopen(o.c_str(), "wb");
+				if (!t.bst) { perror(o.c_str()); return 2; }
+			}
 		}
 	std::vector<void *> dev_obj(devices.size(), nullptr);
 	if (!parse_only)
@@ -372,6 +392,27 @@ int main(int argc, char **argv)
 						le[4 * k] = (uint8_t)n; le[4 * k + 1] = (uint8_t)(n >> 8); le[4 * k + 2] = (uint8_t)(n >> 16); le[4 * k + 3] = (uint8_t)(n >> 24);
 					}
 					fwrite(le, 1, sizeof(le), s.his);
+				}
+			if (s.bst)
+				for (int v = 0; v < 2; v++) { // MVC: the second view's record follows the base view's
+					if (!(v ? fr.samples_mvc : fr.samples)[0]) continue;
+					const int b = 1 << blockstat_log2;
+					// (a bound on the map's size from the frame itself: ceil(w / b) * ceil(h / b) records of four words per plane)
+					std::vector<uint32_t> map(4 * ((size_t)((fr.width_Y + b - 1) / b) * ((fr.height_Y + b - 1) / b) + 2 * (size_t)((fr.width_C + b - 1) / b) * ((fr.height_C + b - 1) / b)));
+					uint16_t dims[6];
+					const int r = F.frame_blockstat(s.dec, &fr, v, blockstat_log2, map.data(), map.size() * 4, dims);
+					if (r) { fprintf(stderr, "e264front_frame_blockstat: %d (%s)\n", r, H.last_error()); _exit(1); }
+					uint8_t hdr[16] = {0};
+					hdr[12] = (uint8_t)blockstat_log2; // (little-endian, 3 .. 6)
+					for (int i = 0; i < 6; i++) { hdr[2 * i] = (uint8_t)dims[i]; hdr[2 * i + 1] = (uint8_t)(dims[i] >> 8); }
+					fwrite(hdr, 1, sizeof(hdr), s.bst);
+					const size_t words = 4 * ((size_t)dims[0] * dims[1] + (size_t)dims[2] * dims[3] + (size_t)dims[4] * dims[5]);
+					std::vector<uint8_t> le(4 * words); // little-endian whatever the host
+					for (size_t k = 0; k < words; k++) {
+						const uint32_t n = map[k];
+						le[4 * k] = (uint8_t)n; le[4 * k + 1] = (uint8_t)(n >> 8); le[4 * k + 2] = (uint8_t)(n >> 16); le[4 * k + 3] = (uint8_t)(n >> 24);
+					}
+					fwrite(le.data(), 1, le.size(), s.bst);
 				}
 			if (s.dif) {
 				for (int v = 0; v < 2 && s.has_kept; v++) { // MVC: the second view's line follows the base view's
@@ -659,6 +700,7 @@ int main(int argc, char **argv)
 		if (s.prev) fclose(s.prev);
 		if (s.dif) fclose(s.dif);
 		if (s.bdf) fclose(s.bdf);
+		if (s.bst) fclose(s.bst);
 		if (s.his) fclose(s.his);
 		F.free_dec(&s.dec);
 	}

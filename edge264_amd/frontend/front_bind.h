@@ -1,5 +1,5 @@
 /*
- * front_bind.h -- internal to libedge264_frontdigest.so (front_digest.c, front_preview.c, front_diff.c, front_hist.c, front_blockdiff.c): the entry points of the front library and of the back end
+ * front_bind.h -- internal to libedge264_frontdigest.so (front_digest.c, front_preview.c, front_diff.c, front_hist.c, front_blockdiff.c, front_blockstat.c): the entry points of the front library and of the back end
  * the four files work through, bound once for all (front_digest.c; e264front_digest_use names the libraries), and the view a frame's planes make
  * in their slot.  Nothing here is exported.
  */
@@ -37,6 +37,7 @@ struct E264FrontBind {
 	int (*frame_diff)(E264Stream *, int, const E264View *, E264Stream *, int, const E264View *, E264Diff *);
 	int (*frame_hist)(E264Stream *, int, const E264View *, E264Hist *);
 	int (*frame_blockdiff)(E264Stream *, int, const E264View *, E264Stream *, int, const E264View *, int, void *, size_t);
+	int (*frame_blockstat)(E264Stream *, int, const E264View *, int, void *, size_t);
 };
 extern HIDDEN struct E264FrontBind e264front_bind;
 

@@ -24,7 +24,7 @@
 
 #include "front_bind.h"
 
-struct E264FrontBind e264front_bind = {ENODEV, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+struct E264FrontBind e264front_bind = {ENODEV, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
 #define g e264front_bind
 static pthread_once_t g_once = PTHREAD_ONCE_INIT;
 
@@ -61,7 +61,8 @@ static void bind_all(void)
 	*(void **)&g.frame_diff = dlsym(hl, "e264hip_frame_diff");
 	*(void **)&g.frame_hist = dlsym(hl, "e264hip_frame_hist");
 	*(void **)&g.frame_blockdiff = dlsym(hl, "e264hip_frame_blockdiff");
-	if (g.stream && g.device_samples && g.slot_of && g.frame_device_ptr && g.frame_digest && g.preview_bytes && g.frame_preview && g.frame_diff && g.frame_hist && g.frame_blockdiff) g.err = 0;
+	*(void **)&g.frame_blockstat = dlsym(hl, "e264hip_frame_blockstat");
+	if (g.stream && g.device_samples && g.slot_of && g.frame_device_ptr && g.frame_digest && g.preview_bytes && g.frame_preview && g.frame_diff && g.frame_hist && g.frame_blockdiff && g.frame_blockstat) g.err = 0;
 }
 
 int e264front_bind_once(void)
@@ -71,8 +72,8 @@ int e264front_bind_once(void)
 }
 
 /* A program that has loaded the front library and the back end itself (dlopen: a build of the front library that lies elsewhere, a variant of the back
- * end) hands over its two handles BEFORE the first e264front_frame_digest, e264front_frame_preview (front_preview.c), e264front_frame_diff (front_diff.c), e264front_frame_hist (front_hist.c) or e264front_frame_blockdiff (front_blockdiff.c), so that the decoders it
- * passes meet the instance that made them.  Without this call the libraries are found as bind_all says.  0, or EINVAL (a null handle) / EALREADY (the first digest, preview, diff, histogram or block difference map has been asked for). */
+ * end) hands over its two handles BEFORE the first e264front_frame_digest, e264front_frame_preview (front_preview.c), e264front_frame_diff (front_diff.c), e264front_frame_hist (front_hist.c), e264front_frame_blockdiff (front_blockdiff.c) or e264front_frame_blockstat (front_blockstat.c), so that the decoders it
+ * passes meet the instance that made them.  Without this call the libraries are found as bind_all says.  0, or EINVAL (a null handle) / EALREADY (the first digest, preview, diff, histogram, block difference map or block statistics map has been asked for). */
 PUBLIC int e264front_digest_use(void *front_lib, void *hip_lib)
 {
 	if (!front_lib || !hip_lib) return EINVAL;

@@ -271,6 +271,55 @@ int  e264hip_blockdiff_batch(E264Device *dev,
                              E264Stream *const *streams_b, const int *slots_b, const E264View *views_b,
                              int n, int log2_block, void *out, size_t pitch);
 
+/* ---- what ONE decoded picture looks like, region by region: the per-block statistics map, computed on the device ---- */
+/* The histogram has no positions, the block difference map needs a second picture, the preview is a mean without a second moment or gradients.
+ * This map answers, block by block, for one picture where it lies: letterbox and pillarbox detection (rows or columns of flat blocks at one level),
+ * regional black or frozen-logo detection, focus and blur meters (gradient energy), texture and activity masks for a downstream encoder's adaptive
+ * quantisation, regions of interest for an inference stage, local mean and variance for auto-exposure -- without reading the picture back.  The
+ * reference has no counterpart (include/edge264_blockstat.h's e264_blockstat_plane does the same arithmetic on an Edge264Frame's plane on the host).
+ *
+ * THE BLOCK STATISTICS MAP, version E264_BLOCKSTAT_VERSION.  k = log2_block in {3, 4, 5, 6}, b = 1 << k.  For plane p of a view, w x h samples s(y, x):
+ *     bw = (w + b - 1) >> k          bh = (h + b - 1) >> k
+ *     record (Y, X) covers the samples y in [b Y, min(b Y + b, h)), x in [b X, min(b X + b, w)):
+ *         sum   = sum s                                sumsq = sum s^2                                  over the block's samples
+ *         gh    = sum |s(y, x + 1) - s(y, x)|          over the block's samples (y, x) with x + 1 < w
+ *         gv    = sum |s(y + 1, x) - s(y, x)|          over the block's samples (y, x) with y + 1 < h
+ * A horizontal pair belongs to the block of its LEFT sample, also when x + 1 lies in the next block; a vertical pair to the block of its TOP
+ * sample.  A pair that would leave the view does not exist.  Nothing is clamped or replicated: a block at the right or bottom edge simply has fewer
+ * samples and pairs.  A picture's map is Y | Cb | Cr, each plane row-major bh x bw records, tight; every plane uses the same b, each over its own
+ * (cropped) view, so the result stays 4:2:0.
+ * Everything is exact: a block has at most 64 x 64 = 4096 samples, so sum, gh and gv are <= 4096 * 255 < 2^21 and sumsq <= 4096 * 255^2 < 2^29; the
+ * accumulators are 32 bits and nothing wraps.
+ * Per plane: the sum of `sum` over the map is sum n bin[n] of the histogram record of the same view and the sum of `sumsq` is sum n^2 bin[n]; the
+ * block difference map of the picture against an all-zero picture of the same view has sad == sum and sse == sumsq, record for record; the sums of
+ * gh and of gv over the map are the plane's total horizontal and vertical variation whatever k (a pair goes to one block only); and with n the
+ * block's sample count, n sumsq - sum^2 >= 0 in 64 bits, zero <=> the block is flat.
+ *
+ * e264hip_blockstat_bytes (host only): the map's size, and in dims (may be NULL) bw, bh of Y, Cb, Cr; 0 for a null view, k outside 3..6 or a plane
+ *   without samples.
+ * e264hip_blockstat_batch: the map of views[i] of slot slots[i] of streams[i] at out + i * pitch; only its e264hip_blockstat_bytes bytes there are
+ *   written, the rest of a pitch is left as it was.  e264hip_frame_blockstat is the batch of one with pitch = cap.  Both BLOCK until `out` (ordinary
+ *   host memory) is filled.
+ * Ordering: one kernel per call, whatever n, queued on the streams' compute lane behind everything queued there -- a map asked for right after
+ *   e264hip_frame_submit, e264hip_submit_batch*, e264hip_frame_fill or e264hip_frame_upload, with no wait between, sees that work's result.  All
+ *   streams of a call belong to `dev` and share one lane, as for a submission (else EINVAL); a stream may appear more than once (the pass only
+ *   reads).  The call waits for its own event, never for the device.
+ * Lifetime: the call marks the lane as a fill does, so a slot freed while it runs stays parked behind it (e264hip_frame_free never hands memory
+ *   back under a kernel); the caller drives the streams, as for a submission.
+ * Errors: EINVAL (and nothing is queued, `out` is untouched) for a null pointer, n < 0, n > E264_BLOCKSTAT_MAX_BATCH, k outside 3..6, a slot out of
+ *   range or not allocated, streams of two devices or two lanes, a view e264hip_view_check refuses for that slot's size, pitch or cap smaller than a
+ *   picture's map, more than E264_BLOCKSTAT_MAX_BYTES in one call; e264hip_last_error() names the cause.  n == 0 returns 0.
+ * e264hip_blockstat_check (host only): e264hip_view_check plus the range of k -- what the two calls ask of one picture; 0 or EINVAL with a text. */
+typedef struct { uint32_t sum, sumsq, gh, gv; } E264BlockStat;   /* 16 bytes: sum s, sum s^2, sum |right - s|, sum |below - s| over the block's samples */
+#define E264_BLOCKSTAT_VERSION 1
+#define E264_BLOCKSTAT_MAX_BATCH 4096
+#define E264_BLOCKSTAT_MAX_BYTES (1u << 28)   /* of one call: the sum of the pictures' maps */
+size_t e264hip_blockstat_bytes(const E264View *v, int log2_block, uint16_t dims[6]);
+int  e264hip_blockstat_check(const E264View *view, size_t slot_bytes, int log2_block);
+int  e264hip_frame_blockstat(E264Stream *s, int slot, const E264View *view, int log2_block, void *out, size_t cap);
+int  e264hip_blockstat_batch(E264Device *dev, E264Stream *const *streams, const int *slots, const E264View *views,
+                             int n, int log2_block, void *out, size_t pitch);
+
 /* ---- batched, device-resident replay (multi-stream front end, benchmarking) ---- */
 /* Uploads a packet once; the handle can then be replayed any number of times with the
  * command bytes already resident in HBM (bench.py's timed region). */
